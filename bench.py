@@ -10,6 +10,11 @@ selection and seed extraction, all kernels, and the copy of the maps back to hos
 N > 1 (launched by torch.distributed.run, one rank per GPU): weak scaling -- every rank
 reconstructs the 20 depth maps of its own scene replica per step; no data-path collective,
 torch.distributed (RCCL) only provides the barrier and the max-over-ranks of the elapsed time.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets the scene up, warms up, times ONE region of exactly K steps and prints the
+JSON line (`value`, `ms_per_step`, the roofline of the timed region from its own device counts).  `--full` adds what takes runs
+of its own: five timed regions with `value` their median, the all-seeds variant, `one_call`, the distinct-scenes variant, the
+CPU baseline with `parity`, the strong-scaling mode at N > 1.  `--dump-outputs DIR` writes the maps of the last timed step.
 """
 import argparse
 import json
@@ -335,12 +340,33 @@ def map_parity_all(gpu, ref, against, bounds, view_ids=None):
             "within_bounds": bool(ok)}
 
 
-def timed_region(coll, ctxs, st, refs, n_calls, warmup, repeats=1, n_keep=None):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, maps, view_ids):
+    """--dump-outputs: the maps a caller of the timed path received for the LAST timed step (one dict of float32 arrays per
+    reference view: depth, dz, conf) as DIR/<name>.npy, the views stacked along the first axis, and the reference view of
+    every row as DIR/view_ids.npy (float64).  Where all views together exceed 64 MB (config C5) a fixed, seeded choice of
+    the views is written: the same rows in every run of the same command."""
+    names = [k for k in ("depth", "dz", "conf") if k in maps[0]]
+    per_view = sum(maps[0][k].size * 4 for k in names) + 8
+    keep = list(range(len(maps)))
+    if per_view * len(maps) > DUMP_LIMIT_BYTES:
+        keep = sorted(np.random.RandomState(0).permutation(len(maps))[:max(1, DUMP_LIMIT_BYTES // per_view)].tolist())
+    os.makedirs(dirname, exist_ok=True)
+    for k in names:
+        np.save(os.path.join(dirname, k + ".npy"), np.stack([np.asarray(maps[i][k], np.float32) for i in keep]))
+    np.save(os.path.join(dirname, "view_ids.npy"), np.asarray([view_ids[i] for i in keep], np.float64))
+
+
+def timed_region(coll, ctxs, st, refs, n_calls, warmup, repeats=1, n_keep=None, keep_last_step=False, keep_first=True):
     """W untimed warm-up calls per host thread, then `repeats` timed regions of exactly n_calls library calls of `refs`
     each, dealt over the host threads (one forked context / HIP stream each), every region bracketed by barrier +
     synchronise on both sides (a library call returns with its maps on the host: the stream is idle when it does);
     returns (per-region max-over-ranks elapsed seconds, stats summed over all regions, the maps of the first and of the
-    last timed call).
+    last timed call).  keep_first=False: the maps of the first timed call are not copied (the copy, a few milliseconds, lies
+    inside the first region: a run with one region only would carry it in `value`); the last call's maps stand in for them.
+    keep_last_step: after the regions, all maps of the last step of the last call are kept too (--dump-outputs).
     The host threads live across warm-up and timed regions, as the threads of a long-running process do: thread
     creation -- and with it the creation of each thread's OpenMP team inside the library (~10 ms) -- is not part of
     a step."""
@@ -369,7 +395,7 @@ def timed_region(coll, ctxs, st, refs, n_calls, warmup, repeats=1, n_keep=None):
             for k in range(n):
                 r = c.reconstruct(st, refs_of(i, k), want_normal=False, out=o)   # synchronous: returns with the maps on the host
                 with lock:
-                    if "res" not in last:
+                    if keep_first and "res" not in last:
                         # (the first n_keep maps of the first timed call: a few milliseconds inside the FIRST region only)
                         last["res"] = [(m["depth"].copy(), m["conf"].copy()) for m in r[:n_keep]]
                         last["shape"] = r[0]["depth"].shape
@@ -415,6 +441,13 @@ def timed_region(coll, ctxs, st, refs, n_calls, warmup, repeats=1, n_keep=None):
     # the maps of the LAST timed call: still in the output buffers of the host thread that finished last
     i_last = int(np.argmax(done_at))
     last["res_last"] = [(m["depth"].copy(), m["conf"].copy()) for m in outs[i_last][:n_keep]]
+    if "res" not in last:
+        # keep_first=False (a plain run): nothing is copied inside the region; the maps are the same in every call (the
+        # `parity` object of a --full run: last_timed_call.bit_identical_to_first)
+        last["res"], last["shape"] = last["res_last"], last["res_last"][0][0].shape
+    if keep_last_step:
+        # everything the caller received for the last step of that call (a call's views are its steps one after the other)
+        last["last_step"] = [{k: m[k].copy() for k in ("depth", "dz", "conf")} for m in outs[i_last][-(n_keep or len(outs[i_last])):]]
     last["batch_shapes"] = [sorted(v) for _, v in sorted(acc.pop("_shape", {}).items())]
     batches = acc.pop("_batches", [])
     last["batches"] = sorted(b for b in batches if b[0] > 0)      # first region: (calls in the batch, ms of the batch, ms since the start when it returned)
@@ -738,9 +771,20 @@ def main():
                          "for several seconds so that an outside utilisation sampler sees the run")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps steps, barrier + synchronise on both sides) is run this many "
-                         "times in the same process; `value` is the median region, `repeats` lists them all")
+                         "times in the same process; `value` is the median region, `repeats` lists them all.  Default: 1 "
+                         "(--steps is the number of timed steps of the run), 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, each a run of its own after the timed region: five timed regions "
+                         "instead of one, the all-seeds variant, the `one_call` object, the distinct-scenes variant, the CPU baseline "
+                         "with the `parity` object, and at N > 1 the strong-scaling mode next to the weak line.  Without it the "
+                         "run sets up, warms up, times --steps steps and prints the line; the --no-* switches and "
+                         "--distinct-scenes / --one-call-n select among the parts of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps the timed path returned for its last step (depth, dz, conf of "
+                         "every reference view of the step, float32) to DIR/<name>.npy; the scene is the same in every run "
+                         "of the same command, so two builds can be compared map for map")
     ap.add_argument("--one-call-n", type=int, default=50, help="library calls behind the `one_call` object")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--distinct-scenes", type=int, default=-1,
@@ -762,6 +806,8 @@ def main():
                     help="steps (passes over the rank's reference views) handed to ONE mi_dmrecon_reconstruct batch. "
                          "0 = the largest divisor of --steps that is <= 5")
     args = ap.parse_args()
+    full = args.full
+    n_regions = max(1, args.repeats if args.repeats is not None else (5 if full else 1))
     rank, world, local_rank = rank_world()
     if world == 1 and args.gpus > 1:
         # `python bench.py --gpus N` by itself: start the N ranks (one process per GPU, rank r on device r) the way the driver's
@@ -808,20 +854,24 @@ def main():
         mine = rank_views(all_views, rank, world, mode)
         if not mine:                                        # more ranks than views: this rank only keeps the barriers
             els = []
-            for _ in range(max(1, args.repeats)):
+            for _ in range(n_regions):
                 coll.barrier(); coll.barrier()
                 els.append(coll.max(0.0))
             return els, {}, {}, 0
-        el, acc, last = timed_region(coll, ctxs, st, mine * spc, n_calls, args.warmup, repeats=max(1, args.repeats), n_keep=len(mine))
+        el, acc, last = timed_region(coll, ctxs, st, mine * spc, n_calls, args.warmup, repeats=n_regions, n_keep=len(mine),
+                                     keep_last_step=bool(args.dump_outputs), keep_first=full)
+        last["views"] = mine
         return el, acc, last, len(mine) * spc * n_calls
 
     elapsed_all, acc, last, n_maps_rank = run_mode(args.scaling if world > 1 else "weak")
+    if args.dump_outputs and rank == 0 and last.get("last_step"):
+        dump_outputs(args.dump_outputs, last["last_step"], last["views"])
     n_rep = len(elapsed_all)
     elapsed = float(np.median(elapsed_all))                 # the headline: the median region
     elapsed_sum = float(np.sum(elapsed_all))                # the statistics are summed over all regions
     n_maps = int(round(coll.sum(n_maps_rank)))              # depth maps of ONE region, all ranks
     strong = None
-    if world > 1 and args.scaling == "weak":
+    if full and world > 1 and args.scaling == "weak":
         s_all, _, _, s_rank = run_mode("strong")
         s_el = float(np.median(s_all))
         s_maps = int(round(coll.sum(s_rank)))
@@ -836,7 +886,7 @@ def main():
     # `value`, never as `value`.  Only where the default is in force and the run is the plain one-GPU line.
     seed_env = os.environ.get("MI_DMRECON_SEED_REOPT")
     seed_variant = None
-    if world == 1 and seed_env is None and not args.no_seed_variant:
+    if full and world == 1 and seed_env is None and not args.no_seed_variant:
         os.environ["MI_DMRECON_SEED_REOPT"] = "0"
         try:
             mine = rank_views(all_views, rank, world, "weak")
@@ -849,13 +899,13 @@ def main():
             del os.environ["MI_DMRECON_SEED_REOPT"]
 
     one_call = None
-    if rank == 0 and world == 1 and not args.no_one_call:
+    if full and rank == 0 and world == 1 and not args.no_one_call:
         one_call = run_one_call(ctx, st, all_views, scene, cfg, n_timed=max(1, args.one_call_n))
 
     distinct = None
     n_distinct = args.distinct_scenes if args.distinct_scenes >= 0 else (20 if (args.config == "C3" and world == 1) else 0)
-    if rank == 0 and world == 1 and n_distinct > 0:
-        distinct = run_distinct_scenes(coll, local_rank, cfg, st, n_distinct, spc, n_calls, n_streams, min(args.warmup, 2), max(1, min(args.repeats, 3)))
+    if full and rank == 0 and world == 1 and n_distinct > 0:
+        distinct = run_distinct_scenes(coll, local_rank, cfg, st, n_distinct, spc, n_calls, n_streams, min(args.warmup, 2), min(n_regions, 3))
 
     if rank == 0:
         res = last["res"]
@@ -932,7 +982,7 @@ def main():
             if pred is not None:
                 # (next to the measured sub-object when N > 1; at N = 1 the only thing there is to say about config 4)
                 out.setdefault("strong_scaling", {})["predicted_from_one_gpu"] = pred
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # the maps of the FIRST timed call (first region) and of the LAST one (last region) against the reference's
             last_maps = last.get("res_last", res)
             out["cpu_baseline"], parity = cpu_baseline(scene, cfg, gpu_maps=res[:p.n_views], gpu_maps_last=last_maps[:p.n_views],

@@ -197,6 +197,38 @@ def test_bench_call_plan():
         b.plan_calls(10, 6, 4)
 
 
+def test_bench_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 arrays, the views stacked; above the size limit a fixed choice of the views, the same
+    in every run, within the limit."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_LIMIT_BYTES == 64 << 20
+    rng = np.random.RandomState(3)
+    maps = [{"depth": rng.rand(6, 8).astype(np.float32), "dz": rng.rand(6, 8, 2).astype(np.float32),
+             "conf": rng.rand(6, 8).astype(np.float32), "status": 0} for _ in range(10)]
+    ids = list(range(100, 110))
+    b.dump_outputs(str(tmp_path / "all"), maps, ids)
+    assert sorted(os.listdir(tmp_path / "all")) == ["conf.npy", "depth.npy", "dz.npy", "view_ids.npy"]
+    d = np.load(tmp_path / "all" / "dz.npy")
+    assert d.dtype == np.float32 and d.shape == (10, 6, 8, 2) and np.array_equal(d[7], maps[7]["dz"])
+    assert list(np.load(tmp_path / "all" / "view_ids.npy")) == [float(v) for v in ids]
+    per_view = 6 * 8 * 4 * 4 + 8
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4 * per_view + 5)          # room for four of the ten views
+    b.dump_outputs(str(tmp_path / "s1"), maps, ids)
+    b.dump_outputs(str(tmp_path / "s2"), maps, ids)
+    rows = np.load(tmp_path / "s1" / "view_ids.npy")
+    assert len(rows) == 4 and list(rows) == sorted(set(rows)) and np.array_equal(rows, np.load(tmp_path / "s2" / "view_ids.npy"))
+    total = 0
+    for name in ("depth", "dz", "conf"):
+        a = np.load(tmp_path / "s1" / (name + ".npy"))
+        total += a.nbytes
+        assert np.array_equal(a, np.stack([maps[int(r) - 100][name] for r in rows]))
+    assert total + rows.nbytes <= 4 * per_view + 5
+
+
 # ---- the host half of a call's planning, without a GPU ---------------------------------------------------------------
 
 def _host_views(scene, ref, tables, **kw):

@@ -84,7 +84,7 @@ def test_two_rank_gloo_strong_and_weak_modes(tmp_path):
 
 def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` as the driver types it (no torchrun around it) must start its two ranks itself, bind rank r to
-    device r and print ONE JSON line with n_gpus = 2, the weak value and the strong-scaling sub-object with the ranks' shares.
+    device r and print ONE JSON line with n_gpus = 2, the weak value and (--full) the strong-scaling sub-object with the ranks' shares.
     No GPU here: the ranks load tests/stub/mi_dmrecon_stub.c (a stand-in that computes nothing -- test infrastructure, built
     into a temporary directory; MI_DMRECON_LIB) and share "device 0" over gloo (MI_BENCH_SHARE_GPU=1)."""
     import json
@@ -95,7 +95,7 @@ def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "4", "--warmup", "1",
-                          "--repeats", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                          "--repeats", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -107,6 +107,42 @@ def test_bench_gpus_2_launches_its_own_ranks(tmp_path):
     assert ss["value"] > 0 and ss["views_per_rank"] == [1, 1]            # C1: two reference views, one per rank
     # weak: both ranks reconstruct both views per step; strong: one view each -- twice the weak maps per rank-second at best
     assert d["value"] > ss["value"] * 0.5
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times ONE region of K steps and prints the line without the parts that
+    take runs of their own (--full); --dump-outputs writes the maps of the last timed step as float32 .npy files, the same
+    in two runs of the same command.  On the stand-in library, as above."""
+    import json
+    import numpy as np
+    lib = tmp_path / "libmi_dmrecon_stub.so"
+    subprocess.check_call(["gcc", "-O1", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "stub", "mi_dmrecon_stub.c"), "-o", str(lib)])
+    env = dict(os.environ, MI_DMRECON_LIB=str(lib))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MI_FORCE_DIST"):
+        env.pop(k, None)
+    dumps = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "4", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, env=env, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and len(d["repeats"]) == 1 and d["higher_is_better"] is True
+        assert d["value"] > 0 and d["unit"] == "depth-maps/s" and d["dtype"] == "f32"
+        assert d["ms_per_step"] == pytest.approx(1000.0 * 2 / d["value"])          # C1: two depth maps per step
+        for key in ("one_call", "cpu_baseline", "parity"):
+            assert key not in d, key
+        assert "all_seeds_propagate_variant" not in d["config"] and "distinct_scenes_variant" not in d["config"]
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["conf.npy", "depth.npy", "dz.npy", "view_ids.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    assert a["depth.npy"].shape == (2, 480, 640) and a["dz.npy"].shape == (2, 480, 640, 2) and list(a["view_ids.npy"]) == [0.0, 1.0]
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]), f
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
 
 
 import pytest  # noqa: E402

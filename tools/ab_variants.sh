@@ -6,7 +6,7 @@ OUT=gpurun_out/ab
 mkdir -p $OUT
 for v in "$@"; do
   if [ $v = main ]; then unset MI_DMRECON_LIB; else export MI_DMRECON_LIB=$PWD/build/libmi_dmrecon_$v.so; fi
-  timeout -s KILL 300 python bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --one-call-n 30 > $OUT/$v.json 2> $OUT/$v.err || tail -3 $OUT/$v.err
+  timeout -s KILL 300 python bench.py --steps 5 --warmup 2 --repeats 1 --full --no-cpu-baseline --one-call-n 30 > $OUT/$v.json 2> $OUT/$v.err || tail -3 $OUT/$v.err
   python - <<PY
 import json
 d=json.loads(open("$OUT/$v.json").read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-MI_BENCH_REGION_LOG=1 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err      # the driver's command
+MI_BENCH_REGION_LOG=1 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err      # the driver's command
 python bench.py --streams 1 --steps-per-call 1 --steps 20 --repeats 3 --no-cpu-baseline --no-one-call --distinct-scenes 0 --no-seed-variant > $OUT/bench_1thread.json 2> $OUT/bench_1thread.err
 NOX="--no-cpu-baseline --no-one-call --distinct-scenes 0 --no-seed-variant"      # (the plain line only: nothing but the default form in a profiled run)
 B1="python $R/bench.py --steps 6 --warmup 1 --repeats 1 --streams 1 --steps-per-call 1 $NOX"
@@ -55,6 +55,6 @@ cat $OUT/bench_driver.json $OUT/bench_1thread.json | cut -c1-300
 timeout -s KILL 120 python tools/trace_c3.py > $OUT/round_trace_c3.txt 2>&1
 [ -n "$SKIP_EXTRAS" ] && exit 0                     # (a short collection: the C3 lines, kernel stats and counters only)
 timeout -s KILL 300 python tools/lone_calls.py C3 12 > $OUT/lone_calls.json 2> $OUT/lone_calls.err
-timeout -s KILL 300 python bench.py --config C2 --steps 20 --warmup 3 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-timeout -s KILL 600 python bench.py --config C5 --steps 4 --warmup 1 --repeats 3 --streams 2 --steps-per-call 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+timeout -s KILL 300 python bench.py --config C2 --steps 20 --warmup 3 --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+timeout -s KILL 600 python bench.py --config C5 --steps 4 --warmup 1 --repeats 3 --streams 2 --steps-per-call 1 --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 cut -c1-300 $OUT/lone_calls.json; tail -c 600 $OUT/bench_c5.json
