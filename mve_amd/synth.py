@@ -387,3 +387,63 @@ def make_hard_scene(hp: HardParams = HardParams()) -> SceneData:
         if len(ids) >= 2:
             feats.append(Feature([float(v) for v in pts32[i]], ids))
     return SceneData(cams, imgs, feats)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Scene M1 for the parity fixtures (tests/golden/make_golden_mixed.py): the smooth textured height field of the
+# first scenes under eight UNLIKE cameras -- what every other scene holds constant: image size per view, portrait
+# orientation (the image_aspect < 1 branch of libs/mve/camera.cc:124-144), pixel aspect, an off-centre principal
+# point on odd sizes (image_pyramid.cc:39-44), rolls about the optical axis, very different distances (mip levels
+# 0, 1 and 2 of patch_sampler.cc:85-91 against one reference view) and a view with two pyramid levels only where the
+# rule asks for the third (SingleView::clampLevel, single_view.h:112-123).  No view is smaller than 30 pixels: the
+# reference gives such a view no image at all (the loop of image_pyramid.cc:78 never runs) and crashes on sampling it.
+
+MIXED_SURFACE = SynthParams(bump_amp=0.35)
+
+# (width, height, flen, paspect, ppoint, position, roll about the optical axis [deg], tilt axis, tilt [deg])
+MIXED_VIEWS = (
+    (160, 120, 1.0, 1.0, (0.5, 0.5), (0.0, 0.0, -10.0), 0.0, (1.0, 0.3, 0.0), 0.4),      # 0: plain
+    (120, 160, 1.1, 1.0, (0.5, 0.5), (-0.4, 0.3, -11.5), 0.0, (0.2, 1.0, 0.1), -1.2),     # 1: portrait
+    (161, 121, 2.0, 1.0, (0.46, 0.55), (-1.0, 0.6, -4.4), 0.0, (0.0, 1.0, 0.0), 6.0),    # 2: odd sizes, off-centre ppoint, close
+    (320, 240, 1.0, 1.0, (0.5, 0.5), (-0.8, -0.5, -10.0), 0.0, (0.0, 1.0, 0.0), 4.0),    # 3: twice view 0's density, yawed
+    (160, 120, 1.0, 1.25, (0.5, 0.5), (0.5, -0.6, -10.8), 0.0, (1.0, 0.0, 0.2), 1.0),     # 4: pixel aspect 1.25
+    (96, 72, 1.0, 1.0, (0.5, 0.5), (0.7, 0.7, -7.0), 90.0, (1.0, 1.0, 0.0), 0.8),        # 5: rolled 90 deg, distance 7
+    (160, 120, 0.85, 1.0, (0.5, 0.5), (-0.9, 0.6, -10.3), 180.0, (0.3, 1.0, 0.0), 1.3),  # 6: rolled 180 deg
+    (100, 56, 2.2, 1.0, (0.5, 0.5), (0.5, -0.4, -3.0), 0.0, (0.0, 1.0, 0.0), -2.0),      # 7: two pyramid levels only, very close
+)
+
+
+def mixed_cameras() -> List[Camera]:
+    cams = []
+    for (_, _, flen, paspect, ppoint, pos, roll, axis, tilt) in MIXED_VIEWS:
+        rot = _rodrigues(np.array([0.0, 0.0, 1.0]), np.deg2rad(roll)) @ _rodrigues(np.asarray(axis, np.float64), np.deg2rad(tilt))
+        rot32 = rot.astype(np.float32)
+        trans32 = (-(rot32.astype(np.float64) @ np.asarray(pos, np.float64))).astype(np.float32)
+        cams.append(Camera(flen=flen, paspect=paspect, ppoint=ppoint, rot=[float(v) for v in rot32.reshape(-1)],
+                           trans=[float(v) for v in trans32]))
+    return cams
+
+
+def make_mixed_scene(n_features: int = 1400, seed: int = 29) -> SceneData:
+    """Scene M1.  Every view is rendered and tested for visibility with its OWN size and camera."""
+    p = MIXED_SURFACE
+    cams = mixed_cameras()
+    sizes = [(v[0], v[1]) for v in MIXED_VIEWS]
+    imgs = [_render(p, c, w, h, None, True, False)[0] for c, (w, h) in zip(cams, sizes)]
+    rng = np.random.RandomState(seed)
+    xy = np.stack([rng.uniform(-5.6, 5.6, n_features), rng.uniform(-4.8, 4.8, n_features)], axis=1)
+    # the two close views see a small part of the surface: more features there, or they share none with the others
+    for v, half, n in ((2, 1.3, 160), (7, 0.8, 120)):
+        xy = np.concatenate([xy, np.asarray(MIXED_VIEWS[v][5][:2]) + rng.uniform(-half, half, (n, 2))])
+    pts32 = np.concatenate([xy, surface_height(p, xy[:, 0], xy[:, 1])[:, None]], axis=1).astype(np.float32)
+    vis = []
+    for c, (w, h) in zip(cams, sizes):
+        u, v, z = project(c, w, h, pts32.astype(np.float64))
+        vis.append((z > 0) & (u >= 0) & (u <= w - 1) & (v >= 0) & (v <= h - 1))
+    vis = np.stack(vis, axis=1)
+    feats = []
+    for i in range(len(pts32)):
+        ids = [int(v) for v in np.nonzero(vis[i])[0]]
+        if len(ids) >= 2:
+            feats.append(Feature([float(v) for v in pts32[i]], ids))
+    return SceneData(cams, imgs, feats)

@@ -6,7 +6,9 @@ Run in the authoring container only, after tests/golden/make_golden.py:
 
 Cases: the reference's own depth maps of fixture G1 (view 0, scale 0, RGB) and G1b (view 2, scale 1, RGB level
 image), and a 96x64 stress map (random holes, steps and spikes: ragged borders, depth discontinuities, COMPLEX
-vertices; no colour image).  Each fixture holds the input depth map and the reference's vertices
+vertices; no colour image), and the reference's own maps of scene M1 (tests/golden/make_golden_mixed.py, run first) for
+its portrait view 1 (the image_aspect < 1 branch of the inverse calibration, libs/mve/camera.cc:179-200) and for view 4
+(pixel aspect 1.25).  Each fixture holds the input depth map and the reference's vertices
 (pixel, pos, normal, color, scale, conf) in the reference's vertex order.
 """
 import os
@@ -69,8 +71,18 @@ def main():
     d[holes] = 0
     d[:, :3] = 0; d[50:, 70:] = 0
     run_case(sc1, 1, d.astype(np.float32), None, "stress_96x64", work)
+    mixed_cases(work)
     scene2pset_case(sc1, g1, work)
     shutil.rmtree(work)
+
+
+def mixed_cases(work):
+    """Scene M1: 1/ax differs from 1/ay in both views (a portrait image; pixel aspect 1.25)."""
+    from test_mixed_cameras import load_m1, scene_of
+    m1 = load_m1()
+    scm = scene_of(m1)
+    for v in (1, 4):
+        run_case(scm, v, m1["s0v%d_depth" % v], scm.images[v], "m1_v%d_s0" % v, work)
 
 
 def scene2pset_case(sc1, g1, work):

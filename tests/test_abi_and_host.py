@@ -241,8 +241,12 @@ def test_host_view_selection_is_the_references(g1, g1_scene, h1_scene, w1, w1_sc
     large for tables) against the restatement, which is bit-identical to the reference: the same views for every
     reference view of the fixtures, with 40 global views, with minParallax / globalVSMax / scale / bounding box changed."""
     from oracle import oracle as orc
+    from test_mixed_cameras import load_m1, scene_of
+    m1 = load_m1()
+    m1_scene = scene_of(m1)                                  # scene M1: unlike sizes and intrinsics per view
     for scene, kws in ((g1_scene, [dict(), dict(globalVSMax=2), dict(minParallax=25.0), dict(scale=1)]),
                        (h1_scene, [dict(), dict(minParallax=4.0)]),
+                       (m1_scene, [dict(), dict(globalVSMax=3), dict(scale=1)]),
                        (w1_scene, [dict(globalVSMax=40), dict(globalVSMax=40, minParallax=3.0), dict()])):
         S = orc.OracleScene(scene)
         n = len(scene.cameras)
@@ -255,6 +259,10 @@ def test_host_view_selection_is_the_references(g1, g1_scene, h1_scene, w1, w1_sc
                 for tables in (True, False):
                     assert _host_views(scene, ref, tables, **kw) == want, (n, kw, ref, tables)
     assert _host_views(w1_scene, 0, True, globalVSMax=40) == list(w1["gvs40"])          # the reference binary's own list
+    for ref in range(8):
+        for tables in (True, False):
+            assert _host_views(m1_scene, ref, tables) == list(m1["gvs20_v%d" % ref])
+            assert _host_views(m1_scene, ref, tables, globalVSMax=3) == list(m1["gvs3_v%d" % ref])
     # more than 64 global views (scene W2, 100 views; apps/dmrecon -n 80): the reference binary's own list, both paths, and
     # the library's limit itself (MI_DMRECON_MAX_GLOBAL_VIEWS = 128: every other view of the scene)
     S2 = orc.OracleScene(w2_scene)
