@@ -315,6 +315,60 @@ int  mi_dmrecon_pointset(mi_dmrecon_ctx* ctx, const mi_dmrecon_camera* cam, int3
                          int32_t* pixel, float* pos, float* normal, float* color_out, float* scale, float* conf,
                          int32_t* n_out);
 
+/* ---- the stage after that: the hot loop of apps/fssrecon ----------------------------------------------------------- */
+
+/* fssr::Sample (libs/fssr/sample.h:21-28), field for field. */
+typedef struct mi_dmrecon_fssr_sample_t {
+    float pos[3], normal[3], color[3], scale, confidence;
+} mi_dmrecon_fssr_sample_t;
+
+/* One node of the flattened fssr::Octree (Octree::Node, libs/fssr/octree.h:38-49).  Node 0 is the root; the eight children
+ * of a node are consecutive and lie after it.  The samples are stored in the order Octree::influence_query visits them
+ * (octree.cc:385-399: a node's own samples, then its subtrees 0..7), so a node's samples and those of its subtrees are one
+ * contiguous range that starts with its own. */
+typedef struct mi_dmrecon_fssr_node {
+    int32_t first_child;     /* index of child 0, children 0..7 consecutive; -1: leaf */
+    int32_t first_sample;    /* the node's OWN samples: [first_sample, first_sample + n_samples) */
+    int32_t n_samples;
+    int32_t reserved;
+} mi_dmrecon_fssr_node;
+
+typedef struct mi_dmrecon_fssr_options {
+    int32_t list_capacity;   /* influencing samples a voxel may keep listed (1024 on chip, then up to 15360 in device memory);
+                              * 0 = default = all of that, larger values are clamped to it.  A voxel with more walks the
+                              * tree again instead: slower, the same bits. */
+} mi_dmrecon_fssr_options;
+
+typedef struct mi_dmrecon_fssr mi_dmrecon_fssr;
+
+void mi_dmrecon_fssr_options_default(mi_dmrecon_fssr_options* o);
+
+/* The octree and samples of an fssr::IsoOctree, uploaded once (what IsoOctree::sample_ifn reads through
+ * Octree::influence_query, octree.cc:346-400).  root_center / root_size: Octree::get_root_node_center / _size.
+ * n_nodes == 0 means "no tree": every sample is tested for every voxel, in index order (root_center may be NULL) -- the
+ * cross-check of the walk, with the same results bit for bit.
+ * The tree is checked on the host before anything reaches the GPU; MI_DMRECON_EINVAL for: a negative count (or more than
+ * 2^30); a first_child that is neither -1 nor inside (own index, n_nodes - 8]; a node with two parents; a sample range
+ * outside [0, n_samples]; more than 21 levels (octree.h:26-28, voxel.h:31-35); a root_size that is not positive and
+ * finite; a sample whose scale is not positive and finite (fssr::SampleIO never delivers one). */
+int  mi_dmrecon_fssr_create(mi_dmrecon_ctx* ctx, int64_t n_samples, const mi_dmrecon_fssr_sample_t* samples, int64_t n_nodes,
+                            const mi_dmrecon_fssr_node* nodes, const double root_center[3], double root_size,
+                            mi_dmrecon_fssr** out);
+
+/* IsoOctree::sample_ifn (libs/fssr/iso_octree.cc:93-169, the FSSR_USE_DERIVATIVES branch; evaluate() and
+ * rotation_from_normal, basis_function.cc:20-74; fssr_basis / fssr_weight / gaussian_normalized, basis_function.h:93-164)
+ * at n_voxels positions (3 doubles each: VoxelIndex::compute_position).  Outputs are the fields of fssr::VoxelData
+ * (voxel.h:60-73): value, conf, scale [n], color, deriv [3n]; a voxel no sample influences is all zeros, one whose total
+ * weight is 0 has the reference's NaN.  n_influencing [n]: the size of the influence query's result (iso_octree.cc:99);
+ * max_scale [n]: sample_max_scale (iso_octree.cc:109-112; 0 for an empty voxel).  Every output may be NULL.  May be called
+ * any number of times; a call returns when its outputs are written.  opt == NULL: the defaults. */
+int  mi_dmrecon_fssr_sample(mi_dmrecon_fssr* f, const mi_dmrecon_fssr_options* opt, int64_t n_voxels, const double* positions,
+                            float* value, float* conf, float* scale, float* color, float* deriv,
+                            int32_t* n_influencing, float* max_scale);
+
+/* Frees the device copy.  Destroy it before its context. */
+void mi_dmrecon_fssr_destroy(mi_dmrecon_fssr* f);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ EXPORTS = [
     "mi_dmrecon_num_levels", "mi_dmrecon_level_size", "mi_dmrecon_get_level",
     "mi_dmrecon_global_view_selection", "mi_dmrecon_reconstruct",
     "mi_dmrecon_patch_optimize", "mi_dmrecon_patch_eval", "mi_dmrecon_pointset",
+    "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
 ]
 
 
@@ -63,6 +64,21 @@ class CSettings(ctypes.Structure):
 
 class CPointsetOptions(ctypes.Structure):
     _fields_ = [("dd_factor", ctypes.c_float), ("scale_factor", ctypes.c_float), ("conf_iterations", ctypes.c_int32)]
+
+
+class CFssrSample(ctypes.Structure):
+    """mi_dmrecon_fssr_sample_t = fssr::Sample (libs/fssr/sample.h:21-28)."""
+    _fields_ = [("pos", ctypes.c_float * 3), ("normal", ctypes.c_float * 3), ("color", ctypes.c_float * 3),
+                ("scale", ctypes.c_float), ("confidence", ctypes.c_float)]
+
+
+class CFssrNode(ctypes.Structure):
+    _fields_ = [("first_child", ctypes.c_int32), ("first_sample", ctypes.c_int32), ("n_samples", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class CFssrOptions(ctypes.Structure):
+    _fields_ = [("list_capacity", ctypes.c_int32)]
 
 
 class CProgress(ctypes.Structure):
@@ -161,6 +177,14 @@ def load_library() -> ctypes.CDLL:
     L.mi_dmrecon_debug_plan_views_host.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, ctypes.POINTER(CSettings), i32, i32, i32, vp,
                                                    ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double), i32, vp, vp,
                                                    ctypes.POINTER(i32)]                                     # test hook
+    if hasattr(L, "mi_dmrecon_fssr_create"):       # (a stand-in library of the tests has the entry points of its own time only)
+        i64 = ctypes.c_int64
+        L.mi_dmrecon_fssr_options_default.argtypes = [ctypes.POINTER(CFssrOptions)]
+        L.mi_dmrecon_fssr_options_default.restype = None
+        L.mi_dmrecon_fssr_create.argtypes = [vp, i64, vp, i64, vp, vp, ctypes.c_double, ctypes.POINTER(vp)]
+        L.mi_dmrecon_fssr_sample.argtypes = [vp, ctypes.POINTER(CFssrOptions), i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mi_dmrecon_fssr_destroy.argtypes = [vp]
+        L.mi_dmrecon_fssr_destroy.restype = None
     _lib = L
     return L
 
@@ -579,6 +603,75 @@ class Context:
         if rc < 0:
             _raise(rc)
         return {k: v[:n.value] for k, v in out.items()}
+
+    def fssr_open(self, samples, nodes=None, root_center=None, root_size=None) -> "FssrSampler":
+        """The octree and samples of an fssr::IsoOctree on the GPU (mi_dmrecon_fssr_create).
+
+        ``samples``: (S, 11) float32 rows pos[3], normal[3], color[3], scale, confidence (fssr::Sample), in the order
+        Octree::influence_query visits them; ``nodes``: (N, 4) int32 rows first_child, first_sample, n_samples, 0 with
+        the root first, or None for "no tree" (every sample is tested for every voxel)."""
+        return FssrSampler(self, samples, nodes, root_center, root_size)
+
+
+class FssrSampler:
+    """IsoOctree::sample_ifn (libs/fssr/iso_octree.cc:93-169) at arbitrary positions; see Context.fssr_open."""
+
+    def __init__(self, ctx: Context, samples, nodes=None, root_center=None, root_size=None):
+        self._L = ctx._L
+        self._ctx = ctx                 # the handle uses the context's device and stream
+        self._h = None
+        if not hasattr(self._L, "mi_dmrecon_fssr_create"):
+            raise RuntimeError("%s has no mi_dmrecon_fssr_* entry points: rebuild the library" % LIB_PATH)
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[1] != 11:
+            raise ValueError("samples: (S, 11) float32 expected")
+        n_nodes, cptr, size = 0, None, 0.0
+        if nodes is not None:
+            nodes = np.ascontiguousarray(nodes, np.int32)
+            if nodes.ndim != 2 or nodes.shape[1] != 4:
+                raise ValueError("nodes: (N, 4) int32 expected")
+            if root_center is None or root_size is None:
+                raise ValueError("a tree needs root_center and root_size")
+            n_nodes = len(nodes)
+            center = np.ascontiguousarray(root_center, np.float64).reshape(3)
+            cptr, size = _ptr(center), float(root_size)
+        h = ctypes.c_void_p()
+        rc = self._L.mi_dmrecon_fssr_create(ctx._h, len(samples), _ptr(samples), n_nodes, _ptr(nodes) if n_nodes else None,
+                                            cptr, size, ctypes.byref(h))
+        if rc < 0:
+            _raise(rc)
+        self._h = h
+
+    def sample(self, positions, list_capacity: int = 0) -> dict:
+        """value, conf, scale [n], color, deriv [n, 3] (fssr::VoxelData), n_influencing and max_scale [n] at
+        ``positions`` (n, 3) float64.  ``list_capacity`` (0 = default): see mi_dmrecon_fssr_options."""
+        if self._h is None:
+            raise RuntimeError("the sampler is closed")
+        positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        n = len(positions)
+        out = dict(value=np.zeros(n, np.float32), conf=np.zeros(n, np.float32), scale=np.zeros(n, np.float32),
+                   color=np.zeros((n, 3), np.float32), deriv=np.zeros((n, 3), np.float32),
+                   n_influencing=np.zeros(n, np.int32), max_scale=np.zeros(n, np.float32))
+        opt = CFssrOptions()
+        self._L.mi_dmrecon_fssr_options_default(ctypes.byref(opt))
+        opt.list_capacity = int(list_capacity)
+        rc = self._L.mi_dmrecon_fssr_sample(self._h, ctypes.byref(opt), n, _ptr(positions), _ptr(out["value"]), _ptr(out["conf"]),
+                                            _ptr(out["scale"]), _ptr(out["color"]), _ptr(out["deriv"]),
+                                            _ptr(out["n_influencing"]), _ptr(out["max_scale"]))
+        if rc < 0:
+            _raise(rc)
+        return out
+
+    def close(self):
+        if self._h is not None:
+            self._L.mi_dmrecon_fssr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DMRecon:

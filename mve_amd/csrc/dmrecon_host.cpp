@@ -3553,3 +3553,7 @@ int mi_dmrecon_pointset(mi_dmrecon_ctx* c, const mi_dmrecon_camera* cam, int32_t
 }
 
 }  /* extern "C" */
+
+/* for the other host sources of the library (fssr_host.cpp); not exported (exports.map) */
+int mi_host_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+int mi_host_ctx_device(const mi_dmrecon_ctx* c) { return c ? c->device : -1; }

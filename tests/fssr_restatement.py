@@ -1,0 +1,146 @@
+"""TEST INFRASTRUCTURE ONLY: NumPy restatement of fssr::IsoOctree::sample_ifn (libs/fssr/iso_octree.cc:93-169, the
+FSSR_USE_DERIVATIVES branch) -- the semantics mve_amd/csrc/fssr_device.hip implements, in the reference's own precisions
+(float32 where it computes in float, float64 where it computes in double), brute force over the samples: the influence
+query is the set {s : not (|p - s.pos|^2 > (3 s.scale)^2)} in double, which is what Octree::influence_query returns.
+
+Only the ORDER of the sums differs from the reference (and exp / pow / sqrt come from NumPy), so values agree with it to
+rounding; n and sample_max_scale are exact.
+
+samples: (S, 11) float32 rows pos[3], normal[3], color[3], scale, confidence (= fssr::Sample, sample.h:21-28)."""
+import numpy as np
+
+F32 = np.float32
+PI = 3.14159265358979323846264338327950288
+SQRT_2PI = 2.506628274631000502415765284811045253
+
+
+QUANTITIES = ("value", "conf", "scale", "color", "deriv")
+
+
+def rel_error(q: np.ndarray, q_ref: np.ndarray, rows=None) -> float:
+    """max over `rows` (default: all) of |q - q_ref| / (|q_ref| + m), m = the median |q_ref| over those rows: the error
+    measure of the FSSR tests.  The two must be NaN in the same places (a voxel whose total weight is 0)."""
+    q = np.asarray(q, np.float64).reshape(len(q), -1)
+    r = np.asarray(q_ref, np.float64).reshape(len(q_ref), -1)
+    if rows is not None:
+        q, r = q[rows], r[rows]
+    bad = ~np.isfinite(r)
+    assert np.array_equal(bad, ~np.isfinite(q)), "non-finite values in different places"
+    if bad.all():
+        return 0.0
+    m = np.median(np.abs(r[~bad]))
+    return float(np.max(np.abs(q[~bad] - r[~bad]) / (np.abs(r[~bad]) + m)))
+
+
+def influence_pairs(samples: np.ndarray, positions: np.ndarray, chunk: int = 2048):
+    """(voxel, sample) index pairs of the influence query (octree.cc:389), voxel-major, samples ascending."""
+    spos = samples[:, 0:3].astype(np.float64)
+    r = 3.0 * samples[:, 9].astype(np.float64)
+    thr = r * r
+    vi, si = [], []
+    for v0 in range(0, len(positions), chunk):
+        p = positions[v0:v0 + chunk]
+        d = p[:, None, :] - spos[None, :, :]
+        sq = ((0.0 + d[..., 0] * d[..., 0]) + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        a, b = np.nonzero(~(sq > thr[None, :]))
+        vi.append(a + v0)
+        si.append(b)
+    return np.concatenate(vi), np.concatenate(si)
+
+
+def rotation_from_normal(n: np.ndarray) -> np.ndarray:
+    """basis_function.cc:49-74 for (M, 3) float32 normals -> (M, 3, 3) float32, row-major."""
+    eps = F32(0.001)
+
+    def similar(ref):
+        ok = np.ones(len(n), bool)
+        for j in range(3):
+            ok &= (n[:, j] - eps <= F32(ref[j])) & (F32(ref[j]) <= n[:, j] + eps)
+        return ok
+
+    zero, one = F32(0.0), F32(1.0)
+    with np.errstate(all="ignore"):
+        a = np.stack([n[:, 1] * zero - n[:, 2] * zero, n[:, 2] * one - n[:, 0] * zero, n[:, 0] * zero - n[:, 1] * one], 1)
+        ln = np.sqrt(((zero + a[:, 0] * a[:, 0]) + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2])
+        a = a / ln[:, None]
+        a2 = np.stack([n[:, 1] * a[:, 2] - n[:, 2] * a[:, 1], n[:, 2] * a[:, 0] - n[:, 0] * a[:, 2],
+                       n[:, 0] * a[:, 1] - n[:, 1] * a[:, 0]], 1)
+    R = np.stack([n, a, a2], 1).astype(F32)
+    ident = similar((1, 0, 0))
+    mirror = similar((-1, 0, 0)) & ~ident
+    R[ident] = np.eye(3, dtype=F32)
+    R[mirror] = np.diag([-1, -1, 1]).astype(F32)
+    return R
+
+
+def _sqn(x):
+    return ((0.0 + x[:, 0] * x[:, 0]) + x[:, 1] * x[:, 1]) + x[:, 2] * x[:, 2]
+
+
+def _matvec32(R, d):
+    z = F32(0.0)
+    return np.stack([((z + R[:, i, 0] * d[:, 0]) + R[:, i, 1] * d[:, 1]) + R[:, i, 2] * d[:, 2] for i in range(3)], 1)
+
+
+def sample(samples: np.ndarray, positions: np.ndarray) -> dict:
+    samples = np.ascontiguousarray(samples, F32).reshape(-1, 11)
+    positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+    V = len(positions)
+    vi, si = influence_pairs(samples, positions)
+    n = np.bincount(vi, minlength=V).astype(np.int32)
+    start = np.concatenate([[0], np.cumsum(n)])[:-1]
+
+    # scale cut (iso_octree.cc:109-112): the floor(n/10)-th smallest scale of the voxel's samples, times 2.0f
+    scale = samples[si, 9]
+    order = np.lexsort((scale, vi))
+    nz = n > 0
+    max_scale = np.zeros(V, F32)
+    max_scale[nz] = scale[order][(start + n // 10)[nz]] * F32(2.0)
+    keep = ~(scale > max_scale[vi])
+    vi, si = vi[keep], si[keep]
+
+    s = samples[si]
+    p = positions[vi]
+    R = rotation_from_normal(s[:, 3:6])
+    d = p.astype(F32) - s[:, 0:3]
+    x = _matvec32(R, d).astype(np.float64)
+    sc = s[:, 9].astype(np.float64)
+    sc2 = sc * sc
+    sqn = _sqn(x)
+    with np.errstate(all="ignore"):
+        g = np.exp(-sqn / (2.0 * sc2))
+        value_norm = 2.0 * PI * (sc2 * sc2)
+        deriv_norm = value_norm * 2.0 * sc2
+        vd = np.stack([2.0 * (sc2 - x[:, 0] * x[:, 0]) * g / deriv_norm, (-2.0 * x[:, 0] * x[:, 1]) * g / deriv_norm,
+                       (-2.0 * x[:, 0] * x[:, 2]) * g / deriv_norm], 1)
+        value = x[:, 0] * g / value_norm
+        sr = sqn / sc2
+        inside = ~(sr >= 9.0)
+        df = -4.0 / 3.0 + 48.0 / 54.0 * np.sqrt(sr) - 4.0 / 27.0 * sr
+        wd = np.where(inside[:, None], (df[:, None] * x) / sc[:, None], 0.0)
+        weight = np.where(inside, 1.0 - 2.0 / 3.0 * sr + 8.0 / 27.0 * np.power(sr, 1.5) - 1.0 / 27.0 * (sr * sr), 0.0)
+        Rt = R.transpose(0, 2, 1)
+        vd = _matvec32(Rt, vd.astype(F32)).astype(np.float64)
+        wd = _matvec32(Rt, wd.astype(F32)).astype(np.float64)
+        conf = s[:, 10].astype(np.float64)
+        sigma = (s[:, 9] / F32(5.0)).astype(np.float64)
+        e = p - s[:, 0:3].astype(np.float64)
+        cw = np.exp(-_sqn(e) / (2.0 * (sigma * sigma))) / (sigma * SQRT_2PI) * conf
+        col = (s[:, 6:9] * cw.astype(F32)[:, None]).astype(np.float64)
+
+        def tot(w):
+            return np.bincount(vi, weights=w, minlength=V)
+
+        tv, tw = tot(value * weight * conf), tot(weight * conf)
+        tvd = np.stack([tot((vd[:, i] * weight + wd[:, i] * value) * conf) for i in range(3)], 1)
+        twd = np.stack([tot(wd[:, i] * conf) for i in range(3)], 1)
+        ts, tcw = tot(sc * cw), tot(cw)
+        tc = np.stack([tot(col[:, i]) for i in range(3)], 1)
+        out = {
+            "value": tv / tw, "conf": tw, "scale": ts / tcw, "color": tc / tcw[:, None],
+            "deriv": (tvd * tw[:, None] - twd * tv[:, None]) / (tw * tw)[:, None],
+        }
+    out = {k: np.where((nz if a.ndim == 1 else nz[:, None]), a, 0.0).astype(F32) for k, a in out.items()}
+    out["n_influencing"] = n
+    out["max_scale"] = max_scale
+    return out
