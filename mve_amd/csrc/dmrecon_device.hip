@@ -2346,7 +2346,25 @@ struct XcdRange {
     }
 };
 
-/* flush counters: one atomic per wave (per-view counters live in the first lane of each view slot,
+/* The counter stripe of this workgroup (DevCounterStripe, dmrecon_types.h). */
+__device__ __forceinline__ DevCounters* counter_stripe(DevCounters* counters) {
+    return &reinterpret_cast<DevCounterStripe*>(counters)[blockIdx.x % MI_COUNTER_STRIPES].c;
+}
+/* What a wavefront or a workgroup counted, added to its stripe -- called by ONE lane.  The per-kind words only: the totals
+ * n_eval / n_pass / n_patch are the sums over the kinds and are formed where the stripes are summed (k_round_report).
+ * n_exec: the passes the template executed (k_pass_exec; the plain kernels: n_pass).  err goes to stripe 0 (rare). */
+__device__ __forceinline__ void add_work_counts(DevCounters* counters, int kind, unsigned n_eval, unsigned n_pass, unsigned n_exec,
+                                                unsigned n_patch, unsigned n_filled, unsigned err) {
+    DevCounters* c = counter_stripe(counters);
+    if (n_eval) atomicAdd(&c->k_eval[kind], (unsigned long long)n_eval);
+    if (n_pass) atomicAdd(&c->k_pass[kind], (unsigned long long)n_pass);
+    if (n_exec) atomicAdd(&c->k_pass_exec[kind], (unsigned long long)n_exec);
+    if (n_patch) atomicAdd(&c->k_patch[kind], (unsigned long long)n_patch);
+    if (n_filled) atomicAdd(&c->n_filled, (unsigned long long)n_filled);
+    if (err) atomicOr(&counters->error_flags, err);
+}
+
+/* flush counters: once per wave, to the workgroup's stripe (per-view counters live in the first lane of each view slot,
  * the patch counter in the first lane of each patch) */
 template <class L>
 __device__ __forceinline__ void flush_counters(DevCounters* counters, int lane, unsigned n_eval, unsigned n_pass,
@@ -2360,14 +2378,7 @@ __device__ __forceinline__ void flush_counters(DevCounters* counters, int lane, 
         n_filled += __shfl_down(n_filled, off);
         err |= __shfl_down(err, off);
     }
-    if (lane == 0) {
-        if (n_eval) { atomicAdd(&counters->n_eval, (unsigned long long)n_eval); atomicAdd(&counters->k_eval[kind], (unsigned long long)n_eval); }
-        if (n_pass) { atomicAdd(&counters->n_pass, (unsigned long long)n_pass); atomicAdd(&counters->k_pass[kind], (unsigned long long)n_pass);
-                      atomicAdd(&counters->k_pass_exec[kind], (unsigned long long)n_pass); }
-        if (n_patch) { atomicAdd(&counters->n_patch, (unsigned long long)n_patch); atomicAdd(&counters->k_patch[kind], (unsigned long long)n_patch); }
-        if (n_filled) atomicAdd(&counters->n_filled, (unsigned long long)n_filled);
-        if (err) atomicOr(&counters->error_flags, err);
-    }
+    if (lane == 0) add_work_counts(counters, kind, n_eval, n_pass, n_pass, n_patch, n_filled, err);
 }
 
 /*
@@ -2551,8 +2562,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu((MI_FW >= 
         }
     }
     for (int off = 32; off > 0; off >>= 1) { err |= __shfl_down(err, off); n_exec += __shfl_down(n_exec, off); }
-    if (lane == 0 && err) atomicOr(&a.counters->error_flags, err);
-    if (lane == 0 && n_exec) atomicAdd(&a.counters->k_pass_exec[MI_KIND_SPEC], (unsigned long long)n_exec);
+    if (lane == 0) add_work_counts(a.counters, MI_KIND_SPEC, 0u, 0u, n_exec, 0u, 0u, err);
 }
 
 /*
@@ -2751,13 +2761,7 @@ __global__ __launch_bounds__((SPEC ? MI_TAIL_WAVES : 1) * WAVE) __attribute__((a
         if (SPEC && !single) __syncthreads();                                  /* g_tail_res is reused by the next candidate */
     }
     /* n_eval / n_pass / n_patch / n_filled were kept by lane 0 of wavefront 0 only */
-    if (threadIdx.x == 0) {
-        if (n_eval) { atomicAdd(&a.counters->n_eval, (unsigned long long)n_eval); atomicAdd(&a.counters->k_eval[MI_KIND_TAIL], (unsigned long long)n_eval); }
-        if (n_pass) { atomicAdd(&a.counters->n_pass, (unsigned long long)n_pass); atomicAdd(&a.counters->k_pass[MI_KIND_TAIL], (unsigned long long)n_pass);
-                      atomicAdd(&a.counters->k_pass_exec[MI_KIND_TAIL], (unsigned long long)n_pass); }
-        if (n_patch) { atomicAdd(&a.counters->n_patch, (unsigned long long)n_patch); atomicAdd(&a.counters->k_patch[MI_KIND_TAIL], (unsigned long long)n_patch); }
-        if (n_filled) atomicAdd(&a.counters->n_filled, (unsigned long long)n_filled);
-    }
+    if (threadIdx.x == 0) add_work_counts(a.counters, MI_KIND_TAIL, n_eval, n_pass, n_pass, n_patch, n_filled, 0u);
     for (int off = 32; off > 0; off >>= 1) err |= __shfl_down(err, off);
     if (lane == 0 && err) atomicOr(&a.counters->error_flags, err);
 }
@@ -3246,12 +3250,7 @@ __global__ __launch_bounds__(MI_FRONT_WAVES * WAVE) __attribute__((amdgpu_waves_
         err |= __shfl_down(err, off2); st_att += __shfl_down(st_att, off2);
     }
     if (lane == 0) {
-        if (n_eval) { atomicAdd(&a.counters->n_eval, (unsigned long long)n_eval); atomicAdd(&a.counters->k_eval[MI_KIND_FRONT], (unsigned long long)n_eval); }
-        if (n_pass) { atomicAdd(&a.counters->n_pass, (unsigned long long)n_pass); atomicAdd(&a.counters->k_pass[MI_KIND_FRONT], (unsigned long long)n_pass);
-                      atomicAdd(&a.counters->k_pass_exec[MI_KIND_FRONT], (unsigned long long)n_pass); }
-        if (n_patch) { atomicAdd(&a.counters->n_patch, (unsigned long long)n_patch); atomicAdd(&a.counters->k_patch[MI_KIND_FRONT], (unsigned long long)n_patch); }
-        if (n_filled) atomicAdd(&a.counters->n_filled, (unsigned long long)n_filled);
-        if (err) atomicOr(&a.counters->error_flags, err);
+        add_work_counts(a.counters, MI_KIND_FRONT, n_eval, n_pass, n_pass, n_patch, n_filled, err);
         if (st_att) atomicAdd(&t.job_stats[4 * jobi + 1], st_att);
     }
     if (tid == 0 && member == 0) {
@@ -3457,7 +3456,10 @@ struct SweepArgs {
  * sub-tile by sub-tile: the 16 consecutive entries that form a wavefront of k_optimize<1> lie within a few pixels
  * of each other, their sample windows overlap in every neighbour view, and the texel gathers of a wavefront touch
  * a fraction of the cache lines that 16 hits strung along an image row do (the propagation front crosses a row at
- * isolated pixels).  The order of the list has no influence on the results. */
+ * isolated pixels).  The order of the list has no influence on the results.
+ * (One claim per STRIP of 4 or 8 tiles instead of one per tile -- a quarter or an eighth of the adds on round_work[r] -- was
+ * tried and is slower, 0.53 / 0.57 against 0.39 ms per step: the claims retire in the shadow of the workgroups' load chains,
+ * and a workgroup that scans its tiles one after the other makes that chain longer.  profiles/round_atomics.md.) */
 __global__ __launch_bounds__(256) void k_generate(SweepArgs a) {
     __shared__ unsigned s_wave_cnt[4];
     __shared__ unsigned s_base, s_items, s_ibase;
@@ -3637,7 +3639,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
     __syncthreads();
     if (filled && (threadIdx.x & 63) == 0) atomicAdd(&s_filled, filled);
     __syncthreads();
-    if (threadIdx.x == 0 && s_filled) atomicAdd(&a.counters->n_filled, (unsigned long long)s_filled);
+    if (threadIdx.x == 0) add_work_counts(a.counters, 0, 0u, 0u, 0u, 0u, s_filled, 0u);
 }
 
 /* The write-back of a speculative round (k_optimize_spec): the reference's sequential rule over an entry's candidate
@@ -3717,12 +3719,8 @@ __global__ __launch_bounds__(256) void k_apply_spec(ApplyArgs a) {
         if (n_patch) atomicAdd(&s_red[3], n_patch);
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_red[0]) atomicAdd(&a.counters->n_filled, (unsigned long long)s_red[0]);
-        if (s_red[1]) { atomicAdd(&a.counters->n_eval, (unsigned long long)s_red[1]); atomicAdd(&a.counters->k_eval[MI_KIND_SPEC], (unsigned long long)s_red[1]); }
-        if (s_red[2]) { atomicAdd(&a.counters->n_pass, (unsigned long long)s_red[2]); atomicAdd(&a.counters->k_pass[MI_KIND_SPEC], (unsigned long long)s_red[2]); }
-        if (s_red[3]) { atomicAdd(&a.counters->n_patch, (unsigned long long)s_red[3]); atomicAdd(&a.counters->k_patch[MI_KIND_SPEC], (unsigned long long)s_red[3]); }
-    }
+    /* (the passes EXECUTED are counted by k_optimize_spec) */
+    if (threadIdx.x == 0) add_work_counts(a.counters, MI_KIND_SPEC, s_red[1], s_red[2], 0u, s_red[3], s_red[0], 0u);
 }
 
 /* Seeds (dmrecon.cc:297-330): several features may round to the same pixel; the sequential
@@ -3758,10 +3756,10 @@ __global__ __launch_bounds__(256) void k_apply_seeds(ApplyArgs a) {
     }
     const unsigned long long m = __ballot(newly);
     if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1)
-        atomicAdd(&a.counters->n_filled, (unsigned long long)__popcll(m));
+        add_work_counts(a.counters, MI_KIND_SEED, 0u, 0u, 0u, 0u, (unsigned)__popcll(m), 0u);
     const unsigned long long m2 = __ballot(okseed);
     if (m2 && (threadIdx.x & 63) == __ffsll((long long)m2) - 1)
-        atomicAdd(&a.counters->n_seeds_ok, (unsigned long long)__popcll(m2));
+        atomicAdd(&counter_stripe(a.counters)->n_seeds_ok, (unsigned long long)__popcll(m2));
 }
 
 /* ------------------------------------------------------------------------- */
@@ -3846,7 +3844,29 @@ __global__ __launch_bounds__(256) void k_round_report(const unsigned* __restrict
     const int tid = (int)threadIdx.x;
     for (int i = tid; i < n_a; i += 256) out_rw[i] = a[i];
     for (int i = tid; i < n_b; i += 256) out_rw[n_a + i] = b[i];
-    if (tid < (int)(sizeof(DevCounters) / sizeof(unsigned))) out_hc[tid] = reinterpret_cast<const unsigned*>(counters)[tid];
+    /* the counters: the sum of the stripes, 64-bit word by word (error_flags | pad: the OR -- the flags are set on stripe 0
+     * only); then the totals the device does not add itself: the sums over the kinds */
+    constexpr int CW = (int)(sizeof(DevCounters) / sizeof(unsigned long long));
+    static_assert(sizeof(DevCounters) % sizeof(unsigned long long) == 0 && CW <= 256 && offsetof(DevCounters, error_flags) % 8 == 0, "summed as 64-bit words");
+    __shared__ unsigned long long s_cnt[CW];
+    if (tid < CW) {
+        const bool flags = tid == (int)(offsetof(DevCounters, error_flags) / 8);
+        unsigned long long v = 0;
+        for (int s = 0; s < MI_COUNTER_STRIPES; ++s) {
+            const unsigned long long w = reinterpret_cast<const unsigned long long*>(&reinterpret_cast<const DevCounterStripe*>(counters)[s].c)[tid];
+            v = flags ? (v | w) : (v + w);
+        }
+        s_cnt[tid] = v;
+    }
+    __syncthreads();
+    if (tid < CW) {
+        unsigned long long v = s_cnt[tid];
+        const int k0 = tid == (int)(offsetof(DevCounters, n_eval) / 8) ? (int)(offsetof(DevCounters, k_eval) / 8)
+                     : tid == (int)(offsetof(DevCounters, n_pass) / 8) ? (int)(offsetof(DevCounters, k_pass) / 8)
+                     : tid == (int)(offsetof(DevCounters, n_patch) / 8) ? (int)(offsetof(DevCounters, k_patch) / 8) : -1;
+        if (k0 >= 0) for (int k = 0; k < 8; ++k) v += s_cnt[k0 + k];
+        out_hc[2 * tid] = (unsigned)v; out_hc[2 * tid + 1] = (unsigned)(v >> 32);
+    }
     static_assert(offsetof(DevJob, n_filled) == offsetof(DevJob, flags) + 4, "flags and n_filled are read as a pair");
     for (int j = tid; j < n_jobs; j += 256) {
         out_dyn[3 * j] = (unsigned)jobs[j].flags;
@@ -3966,7 +3986,9 @@ static void launch_optimize(hipStream_t s, int lanes_per_view, unsigned grid_blo
     grid_blocks = (grid_blocks + MI_XCDS - 1) / MI_XCDS * MI_XCDS;      /* (XcdRange: every XCD the same number of workgroups) */
     OptArgs a;
     a.follow_seg = follow_seg; a.follow_seg_in = follow_seg_in; a.follow_mask = follow_mask;
-    { const char* e = getenv("MI_DMRECON_DEBUG_SCRAMBLE"); a.scramble = (e && follow_in == nullptr && hyp == nullptr) ? (unsigned)atoi(e) : 0u; }
+    /* (an experiment switch: read once per process, not at every one of the hundreds of launches of a call) */
+    static const unsigned scramble_env = [] { const char* e = getenv("MI_DMRECON_DEBUG_SCRAMBLE"); return e ? (unsigned)atoi(e) : 0u; }();
+    a.scramble = (follow_in == nullptr && hyp == nullptr) ? scramble_env : 0u;
     a.jobs = jobs; a.views = views; a.lut = lut; a.st = st; a.work = work; a.hyp = hyp; a.results = results;
     a.n_work_ptr = n_work_ptr; a.n_work = n_work; a.min_work = min_work; a.max_work = max_work;
     a.round = round; a.counters = counters; a.tbuf = mi_debug_tbuf;

@@ -227,7 +227,9 @@ std::atomic<int> g_inject_footprint(-1);     /* test hook, see fill_job */
 #define MI_MERGE_WINDOW_BIG_US 3000 /* ... from this size on this long: ~2 % of such a call's own time (see mi_dmrecon_reconstruct) */
 #define MI_SINGLE_FOLLOW 4         /* follow-up launches of one attempt per entry in a large round (BatchRun::bulk_rounds) */
 #define MI_FAST_FOLLOW 0           /* of them, the first n in the FAST kernel (MI_DMRECON_FAST_FOLLOW) */
-#define MI_FOLLOW_LISTS 64         /* follow-up list counters per round: five lists x MI_FOLLOW_SEGS segments in use (BatchRun::bulk_rounds) */
+#define MI_BULK_UNITS 4            /* list units per wavefront the grids of the large rounds are sized for (BatchRun::bulk_rounds) ... */
+#define MI_BULK_MIN_WAVES 16384u   /* ... but no grid that would be larger than this is made smaller than this */
+#define MI_FOLLOW_LISTS (5 * MI_FOLLOW_SEGS)   /* follow-up list counters per round: five lists x MI_FOLLOW_SEGS segments (BatchRun::bulk_rounds) */
 #define MI_ONE_LAUNCH_MAX 100000u  /* host-visible rounds below this many entries: one launch instead of first + follow-up */
 #define MI_SPEC_ROUNDS 400000u      /* throughput rounds below this many entries try an entry's candidate hypotheses at the same time */
 #define MI_VIEW_HANDOVER 320u      /* a view leaves the throughput layout once a round's list of its own is shorter than this */
@@ -467,7 +469,10 @@ struct mi_dmrecon_ctx {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;           /* copies of finished views back to the host while the front kernel still runs */
     std::shared_ptr<SceneStore> sc;
-    DevCounters* d_counters = nullptr;
+    DevCounters* d_counters = nullptr;       /* MI_COUNTER_STRIPES copies (DevCounterStripe); k_round_report hands on their sum */
+    /* list units (of 16 patches) per wavefront the grids of the bulk launches are sized for: MI_DMRECON_BULK_UNITS=<n>, read once
+     * when the context is created (a fork takes its parent's); k_optimize strides over its list, same maps for every value */
+    int bulk_units = MI_BULK_UNITS;
     DevBuf<uint8_t> d_stage;
     DevBuf<uint8_t> d_stage2;
     int stage_flip = 0;
@@ -1440,8 +1445,8 @@ static int create_streams(mi_dmrecon_ctx* c) {
 /* The runtime gives a stream its hardware queue when the stream is first used -- tens of milliseconds, which used to land
  * in whichever call first led a batch on this context (the second stream: in its first front phase): used once here. */
 static int warm_streams(mi_dmrecon_ctx* c) {
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(DevCounters), c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(DevCounters), c->stream2));
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, MI_COUNTER_BYTES, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, MI_COUNTER_BYTES, c->stream2));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream2));
     return 0;
@@ -1457,6 +1462,7 @@ int mi_dmrecon_ctx_create(int device, mi_dmrecon_ctx** out) {
     c->device = device;
     c->sc = std::make_shared<SceneStore>();
     c->sc->device = device;
+    if (const char* e = std::getenv("MI_DMRECON_BULK_UNITS")) c->bulk_units = std::max(1, std::min(16, std::atoi(e)));
     if (int rc = create_streams(c)) return rc;
     /* sRGB -> linear table: the formula documented at mvs_tools.cc:22-29 evaluated in double and
      * rounded to float reproduces the literal table at :30-93 bit for bit (tests/test_host_logic.py). */
@@ -1468,7 +1474,7 @@ int mi_dmrecon_ctx_create(int device, mi_dmrecon_ctx** out) {
     lut[255] = 1.0f;
     HIP_TRY(hipMalloc((void**)&c->sc->d_lut, sizeof(lut)));
     HIP_TRY(hipMemcpy(c->sc->d_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&c->d_counters, sizeof(DevCounters)));
+    HIP_TRY(hipMalloc((void**)&c->d_counters, MI_COUNTER_BYTES));
     if (int rc = warm_streams(c)) return rc;
     *out = c;
     return 0;
@@ -1493,8 +1499,9 @@ int mi_dmrecon_ctx_fork(mi_dmrecon_ctx* parent, mi_dmrecon_ctx** out) {
     mi_dmrecon_ctx* c = new mi_dmrecon_ctx;
     c->device = parent->device;
     c->sc = parent->sc;
+    c->bulk_units = parent->bulk_units;
     if (int rc = create_streams(c)) return rc;
-    HIP_TRY(hipMalloc((void**)&c->d_counters, sizeof(DevCounters)));
+    HIP_TRY(hipMalloc((void**)&c->d_counters, MI_COUNTER_BYTES));
     if (int rc = warm_streams(c)) return rc;
     *out = c;
     return 0;
@@ -1972,7 +1979,7 @@ int BatchRun::upload() {
     if (c->bs.d_jobs_packed.reserve(((size_t)nj * job_bytes + 3) / 4)) return fail(MI_DMRECON_EDEVICE, "hipMalloc(jobs) failed");
     HIP_TRY(hipMemcpyAsync(c->bs.d_jobs_packed.p, c->bs.h_up + up_jobs, (size_t)nj * job_bytes, hipMemcpyHostToDevice, S));
     mi_launch_unpack_jobs(S, c->bs.d_jobs_packed.p, (unsigned)(job_bytes / 4), c->bs.d_jobs.p, nj);
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(DevCounters), S));
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, MI_COUNTER_BYTES, S));
     if (c->bs.d_hyp.reserve(std::max<size_t>(n_seeds_total, 1)) || c->bs.d_keyoff.reserve(nj)
         || c->bs.d_round_work.reserve(MI_MAX_ROUNDS) || c->bs.d_round_work_t.reserve(MI_MAX_ROUNDS) || c->bs.d_round_items.reserve(MI_MAX_ROUNDS)
         || c->bs.d_follow_cnt.reserve(MI_FOLLOW_LISTS * MI_MAX_ROUNDS) || c->bs.d_view.reserve(4 * (size_t)nj)
@@ -2126,7 +2133,13 @@ int BatchRun::bulk_rounds(bool& to_tail) {
         ev.end(S);
         const unsigned* n_thr_p = c->bs.d_round_work_t.p + r; const unsigned* n_lat_p = c->bs.d_round_work.p + r;
         const unsigned est = std::max(2u * known_thr, 65536u);
-        const unsigned waves = (est + ppw - 1) / ppw;
+        /* The grid of a large round is sized for MI_BULK_UNITS units of ppw patches per wavefront (k_optimize strides over the list):
+         * a wavefront's prologue (table load, barrier) and its counter flush are paid once per that many units -- 1 / 2 / 4 units:
+         * 1 885 / 1 904 / 1 933 depth-maps/s at the driver's plan (profiles/round_atomics.md).  Never below MI_BULK_MIN_WAVES
+         * wavefronts, several times what the GPU holds at once: the rounds of a call that cannot fill it keep a wavefront per unit.
+         * (MI_DMRECON_BULK_UNITS=<n>, read when the context is created: the A/B switch; same maps) */
+        const unsigned waves1 = (est + ppw - 1) / ppw;
+        const unsigned waves = std::max((waves1 + (unsigned)c->bulk_units - 1) / (unsigned)c->bulk_units, std::min(waves1, MI_BULK_MIN_WAVES));
         /* a view can be in the latency layout from round 2 on (from round 1 if told so): which rounds have such entries is
          * decided on the device -- the launches for them are part of every round (empty ones cost microseconds) */
         const bool any_lat = !wide && (r >= 2 || handover >= 1000000000u);
@@ -2173,7 +2186,8 @@ int BatchRun::bulk_rounds(bool& to_tail) {
              * later ones -- the A/B switch; same maps): the first launch leaves a mask per wavefront unit, two small kernels make the
              * list from the masks -- a wavefront of it then holds entries of one view and a few image rows instead of 16 strangers,
              * whose footprint gathers share no cache line (1.76 x slower per sampling pass: OptArgs::follow_mask). */
-            const bool ordered = SINGLE_FOLLOW && !std::getenv("MI_DMRECON_DEBUG_SCRAMBLE")
+            static const bool scrambled = std::getenv("MI_DMRECON_DEBUG_SCRAMBLE") != nullptr;   /* (read once per process, as the launcher does) */
+            const bool ordered = SINGLE_FOLLOW && !scrambled
                 && [] { const char* e = std::getenv("MI_DMRECON_FOLLOW_ORDERED"); return !e || std::atoi(e) != 0; }();
             if (ordered && (c->bs.d_fmask.reserve(total_px / ppw + 4096) || c->bs.d_fblk.reserve(1024)))
                 return fail(MI_DMRECON_EDEVICE, "hipMalloc(follow-up masks) failed");
@@ -2293,7 +2307,8 @@ int BatchRun::bulk_rounds(bool& to_tail) {
         if (last_thr != 0) return fail(MI_DMRECON_EDEVICE, "internal: throughput entries after the hand-over");
         tail_known = last_lat;
         /* counters as of the end of the host-visible rounds (slot 2 of the poll buffer; read after the call) */
-        HIP_TRY(hipMemcpyAsync(&c->bs.h_poll[2].hc, c->d_counters, sizeof(hc), hipMemcpyDeviceToHost, S));
+        mi_launch_round_report(S, nullptr, 0, nullptr, 0, c->d_counters, c->bs.d_jobs.p, 0, c->bs.h_poll[2].rw, &c->bs.h_poll[2].hc, nullptr, nullptr);   /* (sums the stripes) */
+        HIP_TRY(hipGetLastError());
         have_handover = true;
         to_tail = true;
         return 0;
@@ -2699,7 +2714,8 @@ int BatchRun::front_rounds() {
             mi_launch_round_report(S, d_stats, 4 * nj, nullptr, 0, c->d_counters, c->bs.d_jobs.p, nj, h_done + nj, &P.hc, dyn_of(0), nullptr);
             HIP_TRY(hipGetLastError());
         } else {
-            HIP_TRY(hipMemcpyAsync(&P.hc, c->d_counters, sizeof(hc), hipMemcpyDeviceToHost, S));
+            mi_launch_round_report(S, nullptr, 0, nullptr, 0, c->d_counters, c->bs.d_jobs.p, 0, P.rw, &P.hc, nullptr, nullptr);   /* (sums the stripes) */
+            HIP_TRY(hipGetLastError());
             HIP_TRY(read_dyn(0));
             HIP_TRY(hipMemcpyAsync(front_stats.data(), d_stats, 4 * (size_t)nj * sizeof(unsigned), hipMemcpyDeviceToHost, S));
         }
@@ -3276,7 +3292,7 @@ static int mi_dmrecon_patch_optimize_impl(mi_dmrecon_ctx* c, const mi_dmrecon_se
     HIP_TRY(hipMemcpyAsync(c->bs.d_jobs.p, dj.data(), sizeof(DevJob), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->bs.d_work.p, ent.data(), n * sizeof(DevEntry), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->bs.d_hyp.p, hy.data(), n * sizeof(DevHyp), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(DevCounters), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, MI_COUNTER_BYTES, c->stream));
     /* lanes_per_view = 16 runs the hook through the latency layout, anything else through the throughput layout */
     const int lpv = lanes_per_view == 16 ? 16 : 1;
     if (lpv == 16 && st->nrReconNeighbors > 8)

@@ -170,6 +170,16 @@ struct DevCounters {
      * (s_memtime) and the constant-rate ticks (s_memrealtime) of its own life: their ratio is the clock the kernels ran at */
     unsigned long long clk_shader, clk_real;
 };
+/* On the device the counters are held MI_COUNTER_STRIPES times, each copy on 128-byte lines of its own: a workgroup adds to
+ * stripe blockIdx.x % MI_COUNTER_STRIPES (counter_stripe() in dmrecon_device.hip), so that the tens of thousands of wavefronts of
+ * a bulk launch do not queue up on one word -- a device-scope add on a word that every wavefront adds to retires at one per
+ * ~11 ns, on one of 64 stripes at no measurable cost (tools/ubench/atomic_rate.hip, profiles/atomic_rate.txt).  DevCounters
+ * stays what the host sees: k_round_report sums the stripes.  The device adds the per-kind words only; n_eval, n_pass and
+ * n_patch are formed there as the sums over the kinds.  Rare events (error_flags, n_view_replaced, n_iter14, the clock probe)
+ * stay on stripe 0, which is the DevCounters the pointer names. */
+#define MI_COUNTER_STRIPES 64
+struct alignas(128) DevCounterStripe { DevCounters c; };
+#define MI_COUNTER_BYTES (MI_COUNTER_STRIPES * sizeof(DevCounterStripe))   /* the device buffer; every memset covers all of it */
 enum { MI_KIND_FAST = 0, MI_KIND_FOLLOW = 1, MI_KIND_SEED = 2, MI_KIND_LOOP = 3, MI_KIND_SPEC = 4, MI_KIND_LAT = 5, MI_KIND_TAIL = 6, MI_KIND_FRONT = 7 };
 
 #endif
