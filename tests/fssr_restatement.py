@@ -48,6 +48,26 @@ def influence_pairs(samples: np.ndarray, positions: np.ndarray, chunk: int = 204
     return np.concatenate(vi), np.concatenate(si)
 
 
+def node_levels(nodes: np.ndarray) -> np.ndarray:
+    """Level of every node of a flattened tree (rows first_child, first_sample, n_samples, 0; the root first, children
+    after their parents): 0 for the root, -1 for a node the root does not reach."""
+    lvl = np.full(len(nodes), -1, np.int32)
+    lvl[0] = 0
+    for i in np.nonzero(nodes[:, 0] >= 0)[0]:
+        if lvl[i] >= 0:
+            lvl[nodes[i, 0]:nodes[i, 0] + 8] = lvl[i] + 1
+    return lvl
+
+
+def sample_levels(nodes: np.ndarray, n_samples: int) -> np.ndarray:
+    """Level of the node that holds each sample."""
+    lvl = node_levels(nodes)
+    out = np.full(n_samples, -1, np.int32)
+    for i in np.nonzero(nodes[:, 2] > 0)[0]:
+        out[nodes[i, 1]:nodes[i, 1] + nodes[i, 2]] = lvl[i]
+    return out
+
+
 def rotation_from_normal(n: np.ndarray) -> np.ndarray:
     """basis_function.cc:49-74 for (M, 3) float32 normals -> (M, 3, 3) float32, row-major."""
     eps = F32(0.001)
