@@ -31,12 +31,11 @@
  *   k_pyramid   byte-exact 4x4 Gaussian half-size pyramid (image_tools.h:619-690).
  *
  * No MFMA: every reduction here is a 75-term dot product per lane.
- * Reference citations are relative to /root/reference/libs/dmrecon unless noted.
+ * Reference citations are relative to the reference's libs/dmrecon unless noted.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdlib>
-#include <type_traits>
 
 #include "dmrecon_types.h"
 #include "dmrecon_device.h"
@@ -62,26 +61,13 @@
 /* wavefronts per SIMD the bulk kernels aim for: width 7 needs 18.8 KB of rays / master colours per wavefront in LDS,
  * which caps the occupancy anyway -- let the compiler use the registers */
 #define MI_BULK_WAVES (MI_FW >= 7 ? 1 : MI_WAVES_PER_SIMD)
-/* Words per footprint record.  -DMI_EMU_LIN48 (an experiment, `make variant`): 12 -- the MEMORY side of a record that would hold
- * the footprint's bilinear coefficients as twelve f32 (c00, d1, d2, d3 per channel: no table look-up, no differences in the
- * sampler) instead of four RGBA8 texels: records of 48 bytes, of which the sampler still computes with the first 16 but
- * gathers all 48 (three 16-byte loads kept alive), so that the arithmetic is unchanged and the run shows what the three-fold
- * gather costs by itself (profiles/r6_ab_experiments.txt). */
-#ifdef MI_EMU_LIN48
-#define MI_QUAD_WORDS 12
-#elif defined(MI_QUAD_RECORDS)
-/* the layout of rounds 2-5 (an experiment build now): one 16-byte record per texel position = its 2 x 2 footprint, every texel
- * four times */
-#define MI_QUAD_WORDS 4
-#else
-/* Column pairs (the default since round 6): element (x, y) = texels (x, y), (x, y + 1) -- 8 bytes; a sample's 2 x 2 footprint =
- * elements x and x + 1 of row y = ONE 16-byte gather from an 8-byte aligned address.  Half the bytes per texel position of the
- * 16-byte footprint records (every texel twice instead of four times): the footprints of a wavefront's 16 neighbouring patches cover
- * half as many cache lines, and that -- the lines a wavefront's gathers touch in the vector L1 -- is what the throughput layout's
- * time goes with (profiles/r6_ab_experiments.txt D, I, J: bulk kernels - 4 %, a view's images 12 instead of 20 bytes per texel). */
-#define MI_PAIR_RECORDS 1
-#define MI_QUAD_WORDS 2
-#endif
+/* Footprint elements (DevView::quad, MI_QUAD_WORDS words each) are column pairs: element (x, y) = texels (x, y), (x, y + 1) --
+ * 8 bytes; a sample's 2 x 2 footprint = elements x and x + 1 of row y = ONE 16-byte gather from an 8-byte aligned address.  Half
+ * the bytes per texel position of the 16-byte footprint records of rounds 2-5 (every texel twice instead of four times): the
+ * footprints of a wavefront's 16 neighbouring patches cover half as many cache lines, and that -- the lines a wavefront's gathers
+ * touch in the vector L1 -- is what the throughput layout's time goes with (profiles/r6_ab_experiments.txt D, I, J: bulk
+ * kernels - 4 %, a view's images 12 instead of 20 bytes per texel; 48-byte coefficient records measured
+ * there too, block-linear records in profiles/r5_ab_experiments.txt N). */
 
 namespace MI_FWNS {
 
@@ -92,7 +78,6 @@ typedef u32x2 u32x2_a4 __attribute__((aligned(4)));      /* gfx950 global loads 
  * table lookups.  These typedefs pin them to the global address space (global_load). */
 typedef const __attribute__((address_space(1))) u32x2_a4* gtex2_t;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) u32x4* gtex4_t;
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 typedef const __attribute__((address_space(1))) u32x4_a4* gtex4u_t;   /* dword-aligned 16-byte load */
 typedef const __attribute__((address_space(1))) uint32_t* gtex_t;
@@ -125,33 +110,11 @@ __device__ __forceinline__ void probe_stamp(unsigned id) {
 #define TSTAMP(id) do { } while (0)
 #endif
 
-/* LDS of one 64-lane workgroup = 16 patches (file scope so that the one non-inlined
- * device function below addresses it with ds_* instructions, not flat ones). */
+/* LDS of one 64-lane workgroup = 16 patches (file scope: the device functions below, all of them
+ * inlined into their kernels, name the arrays themselves and so address them with ds_* instructions, not flat ones). */
 __shared__ float g_lut[256];                                   /* sRGB -> linear, mvs_tools.cc:22-93 */
 __shared__ float g_geo[MI_PATCHES_PER_WAVE][MI_NS];            /* 1 / |K^-1 (pixel of sample i)|: the unit-ray scale of PatchSampler::masterViewDirs */
 __shared__ float g_mcol[MI_PATCHES_PER_WAVE][3 * MI_NS];       /* PatchSampler::masterColorSamples */
-#ifdef MI_LDS_WINDOW
-/*
- * LDS windows (north_star: "neighbour-view pixels staged through LDS"; an experiment build, `make variant VFLAGS=-DMI_LDS_WINDOW`).
- * A wavefront of the throughput layout holds 16 neighbouring patches x 4 view slots; the 25 x 16 footprints a pass gathers from one
- * neighbour image lie in a box of a few hundred texels.  Per pass and view slot the wavefront's active lanes find that box (the four
- * window corners of every patch, reduced with LDS atomics -- the lanes of a pass are an arbitrary subset of the wavefront), copy it
- * from the level's plain RGBA8 plane into a tile of MI_WIN_TP x MI_WIN_TH texels with coalesced 16-byte loads, and the samples read
- * their 2 x 2 footprints from the tile (two ds_read2_b32) instead of gathering them from memory.  Whenever the four slots' patches do
- * not share one image and level each, a box does not fit, or a sample falls outside its box (the box comes from the corners), the
- * pass runs on the global gathers -- decided per wavefront and pass; same texels, same arithmetic, same bits either way.
- */
-#ifndef MI_WIN_TP
-#define MI_WIN_TP 28          /* tile pitch = largest box width, texels (a multiple of 4: rows are filled in 16-byte pieces) */
-#endif
-#ifndef MI_WIN_TH
-#define MI_WIN_TH 24          /* largest box height */
-#endif
-__shared__ __attribute__((aligned(16))) uint32_t g_win[4][MI_WIN_TH * MI_WIN_TP];
-__shared__ __attribute__((aligned(16))) int g_wbox[4][4];          /* per view slot: min x, min y, max x, max y (texel indices, inclusive) */
-__shared__ __attribute__((aligned(16))) unsigned g_wimg[4][4];     /* per view slot: the level's plane (address lo, hi), its width, unused */
-__shared__ unsigned g_wstat[4];                                    /* wavefront-passes of this workgroup: on windows, redone after a miss, other images, box too large */
-#endif
 /* LocalViewSelection ncc[] of the throughput layouts: L::PATCHES x DevSettings::ncc_stride floats of DYNAMIC shared memory, sized
  * by the launcher -- 64 per patch unless globalVSMax asks for more (MI_MAX_GLOBAL = 128): the 4 KB a wavefront of 16 patches has
  * always had; 8 KB per wavefront would cost the general kernels a wavefront per SIMD (160 KB per CU, 12 wavefronts) */
@@ -216,78 +179,9 @@ template <> struct ViewPack<8> { typedef unsigned long long type; static constex
 
 template <int LPV, int NV> struct Lay;
 
-/* The value of the lane 16 / 32 lanes away (lane ^ 16, lane ^ 32): exchanges ACROSS the DPP rows of a wavefront, which DPP itself
- * cannot do.  gfx950 has them as VALU instructions -- v_permlane16_swap_b32 vdst, src: the odd rows of vdst and the even rows
- * of src change places (with both = v the partner row's value arrives in the second result for the even rows 0, 2 and in the
- * first for the odd rows 1, 3); v_permlane32_swap_b32: the upper half of vdst and the lower half of src change places -- no
- * trip through the scalar unit (v_readlane + its hazards) or the LDS crossbar (-DMI_T_SHFL: ds_bpermute). */
-#ifdef MI_T_SHFL
-__device__ __forceinline__ int x16(int v) { return __shfl_xor(v, 16); }
-__device__ __forceinline__ int x32(int v) { return __shfl_xor(v, 32); }
-#else
-__device__ __forceinline__ int x16(int v) {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((threadIdx.x & 16u) ? r[0] : r[1]);
-}
-__device__ __forceinline__ int x32(int v) {
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)((threadIdx.x & 32u) ? r[0] : r[1]);
-}
-#endif
-
-/* ---- four view slots (nrReconNeighbors <= 4, the reference's default) */
-#ifdef MI_TRANSPOSED
-/*
- * The throughput layout with the lanes TRANSPOSED: lane = view slot * 16 + patch instead of patch * 4 + view slot.  The same
- * 16 patches x 4 view slots, the same arithmetic in the same order -- the sums over the view slots run (v0 + v1) + (v2 + v3)
- * in both, so the maps are the same bits -- but the 16 lanes of a DPP row now gather from ONE neighbour image, at the
- * positions of 16 patches that lie within a few pixels of each other (k_generate emits a wavefront's entries sub-tile by
- * sub-tile): consecutive lanes ask for records that are neighbours in memory, where the quad layout put four different
- * images side by side (no two consecutive lanes ever shared a cache line, and the texture path looked 64 lines up per
- * gather).  What the quad layout did with DPP quad permutes -- the exchanges across the view slots of a patch: two to nine
- * sums per pass, a few ballots per turn -- crosses DPP rows here: v_permlane16_swap / v_permlane32_swap (gfx950), or an LDS
- * permute (-DMI_T_SHFL).
- */
-template <> struct Lay<1, 4> {
-    static constexpr int LPV = 1, NV = 4, PATCHES = 16;
-    static constexpr bool LAT = false;
-    __device__ static __forceinline__ int vslot(int lane) { return lane >> 4; }
-    __device__ static __forceinline__ int sub(int) { return 0; }
-    __device__ static __forceinline__ int patch(int lane) { return lane & 15; }
-    __device__ static __forceinline__ float view_sum(float v) { return v; }
-    __device__ static __forceinline__ double view_sum(double v) { return v; }
-    __device__ static __forceinline__ bool view_all(bool p) { return p; }
-    __device__ static __forceinline__ float patch_sum(float v) {
-        v = fadd_i(v, x16(__float_as_int(v)));              /* v0 + v1 | v2 + v3 */
-        v = fadd_i(v, x32(__float_as_int(v)));              /* (v0 + v1) + (v2 + v3) */
-        return v;
-    }
-    __device__ static __forceinline__ double patch_sum(double v) {
-        v += dmov(v, x16);
-        v += dmov(v, x32);
-        return v;
-    }
-    __device__ static __forceinline__ unsigned long long patch_or(unsigned long long v) {
-        v |= dmov_u(v, x16); v |= dmov_u(v, x32);
-        return v;
-    }
-    __device__ static __forceinline__ float wave_sum(float v) { return v; }      /* unused in this layout */
-    /* out[k] = v of view slot k of my patch: mine, and my partners' across 16, 32 and 48 lanes */
-    __device__ static __forceinline__ void from_views(int v, int lane, int* out) {
-        const int a = x16(v), b = x32(v), c = x32(a);
-        const int s = lane >> 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = (k == s) ? v : (k == (s ^ 1)) ? a : (k == (s ^ 2)) ? b : c;
-    }
-    template <int S> __device__ static __forceinline__ int view_xor(int v) { return S == 0 ? x16(v) : x32(v); }
-    /* bit k = predicate of view slot k of my patch */
-    __device__ static __forceinline__ unsigned view_ballot(bool p, int lane) {
-        const unsigned long long r = __ballot(p) >> (lane & 15);
-        return (unsigned)((r & 1ull) | ((r >> 15) & 2ull) | ((r >> 30) & 4ull) | ((r >> 45) & 8ull));
-    }
-    __device__ static __forceinline__ unsigned rows_to_lane0(unsigned v) { return v; }
-};
-#else
+/* ---- four view slots (nrReconNeighbors <= 4, the reference's default).  Lane = patch * 4 + view slot: the exchanges across
+ * the view slots of a patch are DPP quad permutes.  (The transposed form, lane = view slot * 16 + patch with the exchanges
+ * across DPP rows, measured slower: profiles/r5_ab_experiments.txt.) */
 template <> struct Lay<1, 4> {
     static constexpr int LPV = 1, NV = 4, PATCHES = 16;
     static constexpr bool LAT = false;
@@ -326,7 +220,6 @@ template <> struct Lay<1, 4> {
     /* per-view counters of the wavefront's one patch summed into lane 0 (latency layouts only) */
     __device__ static __forceinline__ unsigned rows_to_lane0(unsigned v) { return v; }
 };
-#endif
 
 template <> struct Lay<16, 4> {
     static constexpr int LPV = 16, NV = 4, PATCHES = 1;
@@ -354,12 +247,8 @@ template <> struct Lay<16, 4> {
         v &= dpp_xor1(v); v &= dpp_xor2(v); v &= dpp_half_mirror(v); v &= dpp_mirror(v);
         return v != 0;
     }
-    /* inputs are already uniform within each row: four readlanes instead of LDS permutes.  (-DMI_LAT_PERMLANE: the same sums,
-     * (v0 + v1) + (v2 + v3), by two cross-row exchanges x16 / x32 -- v_permlane16/32_swap -- instead of the trip through the
-     * scalar unit.  Measured, same lease: the front of a lone 20-view call 14.8-15.1 ms against 13.4 with the readlanes, the
-     * front of a 400-view batch 2.09 against 1.85 ms per step: the swaps sit in the turn's dependent chain and are slower than
-     * v_readlane + s_nop.) */
-#ifndef MI_LAT_PERMLANE
+    /* inputs are already uniform within each row: four readlanes instead of LDS permutes (two cross-row v_permlane16/32_swap
+     * exchanges instead of the trip through the scalar unit measured slower: profiles/r5_ab_experiments.txt) */
     __device__ static __forceinline__ float patch_sum(float v) {
         const int i = __float_as_int(v);
         return (__int_as_float(__builtin_amdgcn_readlane(i, 0)) + __int_as_float(__builtin_amdgcn_readlane(i, 16)))
@@ -373,18 +262,6 @@ template <> struct Lay<16, 4> {
         const double r3 = __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
         return (r0 + r1) + (r2 + r3);
     }
-#else
-    __device__ static __forceinline__ float patch_sum(float v) {
-        v = fadd_i(v, x16(__float_as_int(v)));
-        v = fadd_i(v, x32(__float_as_int(v)));
-        return v;
-    }
-    __device__ static __forceinline__ double patch_sum(double v) {
-        v += dmov(v, x16);
-        v += dmov(v, x32);
-        return v;
-    }
-#endif
     /* sum over all 64 lanes (inputs arbitrary) */
     __device__ static __forceinline__ float wave_sum(float v) { return patch_sum(view_sum(v)); }
     __device__ static __forceinline__ unsigned long long patch_or(unsigned long long v) {
@@ -646,9 +523,6 @@ struct NView {                   /* my neighbour view at the selected mip level 
     float dx, dy, dz;            /* D: one pixel down */
     int w, h;
     const uint32_t* img;         /* footprint elements of the level (DevView::quad) */
-#ifdef MI_LDS_WINDOW
-    const uint32_t* raw;         /* the level's plain RGBA8 texels (DevView::img): what a wavefront's LDS windows are filled from */
-#endif
 };
 
 /* fold the level's calibration into rows 0, 1: x' = ax.x + cx.z, y' = ay.y + cy.z */
@@ -700,9 +574,6 @@ __device__ __forceinline__ bool setup_view(const DevView* __restrict__ views, co
     premultiply(nv, L.ax, L.ay, L.cx, L.cy);
     nv.w = L.w; nv.h = L.h;
     nv.img = V->quad + MI_QUAD_WORDS * (size_t)L.tex_off;      /* footprint elements of this level */
-#ifdef MI_LDS_WINDOW
-    nv.raw = V->img + L.tex_off;
-#endif
     return true;
 }
 
@@ -724,9 +595,6 @@ struct ViewC {
 __device__ __forceinline__ void viewc_reset(ViewC& vc) {
     vc.sel = -2; vc.lvl = -1; vc.V = nullptr; vc.inv0 = 0.f; vc.maxl = 0;
     vc.nv.w = 0; vc.nv.h = 0; vc.nv.img = nullptr;
-#ifdef MI_LDS_WINDOW
-    vc.nv.raw = nullptr;
-#endif
     vc.nv.sx = vc.nv.sy = vc.nv.sz = vc.nv.ax = vc.nv.ay = vc.nv.az = 0.f;
     vc.nv.bx = vc.nv.by = vc.nv.bz = vc.nv.dx = vc.nv.dy = vc.nv.dz = 0.f;
 }
@@ -758,76 +626,6 @@ struct GNSums {
     double A00, A01, A02, A11, A12, A22, B0, B1, B2;   /* optimizeDepthAndNormal (:312-343), colour scale baked in */
 };
 
-#ifdef MI_LDS_WINDOW
-struct Win { int x0, y0; unsigned limx, limy; const uint32_t* tile; };
-/* Builds the LDS windows of the pass the calling lanes are about to run (see g_win).  Called by an arbitrary subset of a
- * wavefront's lanes; returns the same value in all of them: true = every caller's samples can be read from its slot's tile. */
-__device__ __forceinline__ bool window_build(const PatchState& ps, const NView& nv, const float* __restrict__ geo, int lane, Win& W) {
-    const int slot = lane & 3;
-    const unsigned long long act = __ballot(true);
-    const float wlim = __uint_as_float(__float_as_uint((float)(nv.w - 1)) - 1u), hlim = __uint_as_float(__float_as_uint((float)(nv.h - 1)) - 1u);
-    constexpr float kLo = 1.17549435e-38f;
-    float umin = 3.0e38f, vmin = 3.0e38f, umax = 0.f, vmax = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int di = (c & 1) ? MI_HALF : -MI_HALF, dj = (c & 2) ? MI_HALF : -MI_HALF;
-        const int i = (dj + MI_HALF) * MI_FW + (di + MI_HALF);
-        const float fi = (float)di, fj = (float)dj;
-        const float lam = (ps.depth + fi * ps.dzI + fj * ps.dzJ) * geo[i];
-        const float vx = nv.ax + fi * nv.bx + fj * nv.dx, vy = nv.ay + fi * nv.by + fj * nv.dy, vz = nv.az + fi * nv.bz + fj * nv.dz;
-        const float iz = fast_rcp(nv.sz + lam * vz);
-        const float u = __builtin_amdgcn_fmed3f((nv.sx + lam * vx) * iz - 0.5f, kLo, wlim), v = __builtin_amdgcn_fmed3f((nv.sy + lam * vy) * iz - 0.5f, kLo, hlim);
-        umin = fminf(umin, u); umax = fmaxf(umax, u); vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
-    }
-    /* texel indices, inclusive, one texel of margin (the box of the corners is the box of the window only as far as the patch
-     * projects as a plane; the unit-ray scales bend it by a fraction of a texel); x + 1 / y + 1 = the footprint's far side */
-    int x0 = (int)umin - 1, y0 = (int)vmin - 1, x1 = (int)umax + 2, y1 = (int)vmax + 2;
-    x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0; x1 = x1 > nv.w - 1 ? nv.w - 1 : x1; y1 = y1 > nv.h - 1 ? nv.h - 1 : y1;
-    /* the slot's box and image over the calling lanes */
-    const int4 init = make_int4(0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000);
-    *reinterpret_cast<int4*>(g_wbox[slot]) = init;
-    const unsigned rlo = (unsigned)(uintptr_t)nv.raw, rhi = (unsigned)((uintptr_t)nv.raw >> 32);
-    *reinterpret_cast<uint4*>(g_wimg[slot]) = make_uint4(rlo, rhi, (unsigned)nv.w, 0u);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    atomicMin(&g_wbox[slot][0], x0); atomicMin(&g_wbox[slot][1], y0); atomicMax(&g_wbox[slot][2], x1); atomicMax(&g_wbox[slot][3], y1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const int4 box = *reinterpret_cast<const int4*>(g_wbox[slot]);
-    const uint4 im = *reinterpret_cast<const uint4*>(g_wimg[slot]);
-    const int bw = box.z - box.x + 1, bh = box.w - box.y + 1;
-    const bool other = im.x != rlo || im.y != rhi || im.z != (unsigned)nv.w;
-    const bool large = bw > MI_WIN_TP || bh > MI_WIN_TH;
-    const unsigned long long m_other = __ballot(other), m_large = __ballot(large);
-    if ((m_other | m_large) != 0ull) {
-        /* (why not, per wavefront-pass: g_wstat[2] the slots' patches sample different images or levels, [3] a box does not fit) */
-        if ((int)lane == __ffsll((long long)act) - 1) atomicAdd(&g_wstat[m_other ? 2 : 3], 1u);
-        return false;
-    }
-    /* fill: the boxes' rows in 16-byte pieces, eight pieces per tile row, dealt over the calling lanes (a row's last piece may reach
-     * past the box: it stays inside the pitch, and inside the view's allocation -- the footprint elements follow the planes) */
-    const unsigned nact = (unsigned)__popcll(act);
-    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, 0u));
-#pragma unroll
-    for (int sl = 0; sl < 4; ++sl) {
-        if (!(act & (0x1111111111111111ull << sl))) continue;               /* no caller has a view in this slot */
-        const int4 b = *reinterpret_cast<const int4*>(g_wbox[sl]);
-        const uint4 m = *reinterpret_cast<const uint4*>(g_wimg[sl]);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(((uintptr_t)m.y << 32) | (uintptr_t)m.x);
-        const int sw = (int)m.z, sbw = b.z - b.x + 1, sbh = b.w - b.y + 1;
-        for (unsigned idx = rank; idx < (unsigned)sbh * (MI_WIN_TP / 4u); idx += nact) {
-            const unsigned r = idx / (MI_WIN_TP / 4u), c4 = (idx - r * (MI_WIN_TP / 4u)) * 4u;
-            if ((int)c4 < sbw) {
-                const u32x4 t = *(gtex4u_t)(src + (size_t)(b.y + (int)r) * (size_t)sw + (size_t)(b.x + (int)c4));
-                *reinterpret_cast<u32x4*>(&g_win[sl][r * MI_WIN_TP + c4]) = t;
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    W.x0 = box.x; W.y0 = box.y; W.limx = (unsigned)(bw - 2); W.limy = (unsigned)(bh - 2);
-    W.tile = g_win[slot];
-    return true;
-}
-#endif
-
 /*
  * One pass over the 25 samples of my view (split over the L::LPV lanes of my view slot) at the current
  * patch state.  It always yields the colour sums that getFastNCC / computeColorScale need
@@ -845,7 +643,7 @@ __device__ __forceinline__ bool window_build(const PatchState& ps, const NView& 
  * mvs_tools.cc:97-145); one fused pass here gathers them once.
  * Returns PatchSampler::success[v]; sums are complete (reduced over the view slot) on return.
  */
-template <int MODE, class L, bool WIN = false>
+template <int MODE, class L>
 __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& nv, const float* __restrict__ s_lut,
                                             const float* __restrict__ geo, const float* __restrict__ mcol,
                                             ColorSums& cs_out, GNSums& gn, float* dump_col, float* dump_der, int sub) {
@@ -913,13 +711,8 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
      *   fetched before the first is consumed -- one exposed memory latency per pass instead of two;
      *   throughput layout: a whole row of the 5 x 5 window per gather round (see below).
      * geom2() / consume2() are the same for two samples at once, in packed arithmetic. */
-#ifdef MI_EMU_LIN48
-    struct Pre { int i; bool live; float fx, fy, gu, gv; u32x4 t, e1, e2; };
-    struct Pre2 { int i0, i1; f2 wgt, fx, fy, gu, gv; u32x4 tA, tB, eA1, eA2, eB1, eB2; };
-#else
     struct Pre { int i; bool live; float fx, fy, gu, gv; u32x4 t; };
     struct Pre2 { int i0, i1; f2 wgt, fx, fy, gu, gv; u32x4 tA, tB; };
-#endif
     auto record = [&](float uc, float vc) -> u32x4 {
         /* one aligned 16-byte gather = the sample's 2 x 2 texel footprint (DevView::quad).  The L1 processes a
          * gather lane by lane when the lanes' addresses do not form one contiguous run, and that access rate is what
@@ -927,51 +720,17 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
          * The record index top * w + left as a 24-bit multiply-add in 32 bits (rows and widths are below 2^24, a level
          * below 2^32 texels) instead of a 64-bit multiply-add (6.3 issue cycles against 5.6, and no sign extension);
          * the texel indices by truncation (the coordinates are not negative). */
-#ifdef MI_TILED_QUADS
-        /* experiment: the records block-linear, 8 x 8 per tile (k_quadify), so that records that are neighbours in the image in
-         * BOTH directions are neighbours in memory -- six more VALU instructions per sample in an instruction-bound kernel */
-        const unsigned ux = (unsigned)uc, uy = (unsigned)vc;
-        const unsigned rec = ((__umul24(uy >> 3, (unsigned)(nv.w + 7) >> 3) + (ux >> 3)) << 6) | ((uy & 7u) << 3) | (ux & 7u);
-#else
         const unsigned rec = __umul24((unsigned)vc, (unsigned)nv.w) + (unsigned)uc;
-#endif
-#ifdef MI_PAIR_RECORDS
-        {
-            /* (x, y) (x, y+1) (x+1, y) (x+1, y+1) as they lie in memory -> the order the sampler names them in: x = (x, y), y = (x+1, y),
-             * z = (x, y+1), w = (x+1, y+1) */
-            const u32x4 r = *(gtex4u_t)(nv.img + MI_QUAD_WORDS * (size_t)rec);
-            u32x4 o; o.x = r.x; o.y = r.z; o.z = r.y; o.w = r.w;
-            return o;
-        }
-#else
-        return *(gtex4_t)(nv.img + MI_QUAD_WORDS * (size_t)rec);
-#endif
-    };
-#ifdef MI_EMU_LIN48
-    /* (the other 32 bytes of the 48-byte record: gathered with the first 16, carried to where the sample is consumed -- as twelve
-     * coefficients would be -- and touched there, so that the loads stay in flight as long as the real ones would) */
-    auto record_more = [&](float uc, float vc, int part) -> u32x4 {
-        const unsigned rec = __umul24((unsigned)vc, (unsigned)nv.w) + (unsigned)uc;
-        return *(gtex4_t)(nv.img + MI_QUAD_WORDS * (size_t)rec + 4 * part);
-    };
-#endif
-#ifdef MI_LDS_WINDOW
-    Win win; win.x0 = win.y0 = 0; win.limx = win.limy = 0u; win.tile = nullptr;
-    unsigned win_mx = 0u, win_my = 0u;            /* the largest tile coordinates a sample asked for (unsigned: below the box = huge) */
-    auto record_win = [&](float uc, float vc) -> u32x4 {
-        const unsigned lx = (unsigned)((int)uc - win.x0), ly = (unsigned)((int)vc - win.y0);
-        win_mx = lx > win_mx ? lx : win_mx; win_my = ly > win_my ? ly : win_my;
-        const unsigned cx = lx < win.limx ? lx : win.limx, cy = ly < win.limy ? ly : win.limy;      /* memory-safe; a miss redoes the pass */
-        const uint32_t* t = win.tile + (__umul24(cy, (unsigned)MI_WIN_TP) + cx);
-        u32x4 o; o.x = t[0]; o.y = t[1]; o.z = t[MI_WIN_TP]; o.w = t[MI_WIN_TP + 1];
+        /* (x, y) (x, y+1) (x+1, y) (x+1, y+1) as they lie in memory -> the order the sampler names them in: x = (x, y), y = (x+1, y),
+         * z = (x, y+1), w = (x+1, y+1) */
+        const u32x4 r = *(gtex4u_t)(nv.img + MI_QUAD_WORDS * (size_t)rec);
+        u32x4 o; o.x = r.x; o.y = r.z; o.z = r.y; o.w = r.w;
         return o;
     };
-#endif
-    auto geom_w = [&](int it, auto use_win) -> Pre {
+    /* sample i of the window (live: it counts; a lane with no sample left repeats the last one) */
+    auto geom_at = [&](int i, bool live) -> Pre {
         Pre q;
-        const int iraw = sub + it * L::LPV;
-        q.live = iraw < MI_NS;                         /* L::LPV = 16: second trip only for lanes 0..8 */
-        const int i = q.live ? iraw : (MI_NS - 1);
+        q.live = live;
         q.i = i;
         const int dj = i / MI_FW - MI_HALF, di = i - (i / MI_FW) * MI_FW - MI_HALF;
         const float fi = (float)di, fj = (float)dj;
@@ -996,16 +755,16 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
         /* the bilinear weights: x - floor(x) in one instruction (v_fract_f32: the same value as the subtraction, which is
          * exact) */
         q.fx = __builtin_amdgcn_fractf(uc); q.fy = __builtin_amdgcn_fractf(vc);
-#ifdef MI_LDS_WINDOW
-        if constexpr (decltype(use_win)::value) q.t = record_win(uc, vc); else
-#endif
         q.t = record(uc, vc);
-#ifdef MI_EMU_LIN48
-        q.e1 = record_more(uc, vc, 1); q.e2 = record_more(uc, vc, 2);
-#endif
         return q;
     };
-    auto geom = [&](int it) -> Pre { return geom_w(it, std::false_type{}); };
+    /* the sample my lane takes on trip `it`.  (Two lambdas, not one: written as one body the same arithmetic comes out of the
+     * compiler with other registers and in another order, and tools/isa_same.sh could not hold this file to its parent.) */
+    auto geom = [&](int it) -> Pre {
+        const int iraw = sub + it * L::LPV;
+        const bool live = iraw < MI_NS;                /* L::LPV = 16: second trip only for lanes 0..8 */
+        return geom_at(live ? iraw : (MI_NS - 1), live);
+    };
     auto geom2 = [&](int ita, int itb) -> Pre2 {
         Pre2 q;
         const int ra = sub + ita * L::LPV, rb = sub + itb * L::LPV;
@@ -1037,40 +796,9 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
         q.fx = mk2(__builtin_amdgcn_fractf(uc.x), __builtin_amdgcn_fractf(uc.y));
         q.fy = mk2(__builtin_amdgcn_fractf(vc.x), __builtin_amdgcn_fractf(vc.y));
         q.tA = record(uc.x, vc.x); q.tB = record(uc.y, vc.y);
-#ifdef MI_EMU_LIN48
-        q.eA1 = record_more(uc.x, vc.x, 1); q.eA2 = record_more(uc.x, vc.x, 2); q.eB1 = record_more(uc.y, vc.y, 1); q.eB2 = record_more(uc.y, vc.y, 2);
-#endif
         return q;
     };
     auto consume = [&](const Pre& q) {
-#ifdef MI_EMU_LIN48
-        asm volatile("" : : "v"(q.e1), "v"(q.e2));
-#endif
-#ifdef MI_EXTRA_LDS
-        /* experiment (make variant VFLAGS=-DMI_EXTRA_LDS=6): that many more look-ups in the sRGB table per sample (addresses as
-         * scattered as the real ones), their values thrown away -- is it the LDS the throughput layout waits for? */
-        {
-#pragma unroll
-          for (int k = 0; k < MI_EXTRA_LDS; ++k) { const float xl = s_lut[(q.t.x >> (3 + k)) & 255u]; asm volatile("" : : "v"(xl)); }
-        }
-#endif
-#ifdef MI_EXTRA_VALU
-        /* experiment (make variant VFLAGS=-DMI_EXTRA_VALU=12): that many VALU instructions per sample that compute nothing -- is the
-         * throughput layout's time the time of its VALU instructions? */
-        { float dummy = q.fx;
-#pragma unroll
-          for (int k = 0; k < MI_EXTRA_VALU; ++k) asm volatile("v_mov_b32 %0, %0" : "+v"(dummy));
-        }
-#endif
-#ifdef MI_EXTRA_FMA
-        /* the same question with instructions that are certainly executed at the plain rate: a dependent chain of v_fma_f32 (the
-         * micro-benchmark's instruction, 3.7 cycles each at three wavefronts per SIMD) on a live value */
-        { float dummy = q.fx;
-#pragma unroll
-          for (int k = 0; k < MI_EXTRA_FMA; ++k) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dummy));
-          asm volatile("" : : "v"(dummy));
-        }
-#endif
         const int i = q.i;
         const int dj = i / MI_FW - MI_HALF, di = i - (i / MI_FW) * MI_FW - MI_HALF;
         const float fx = q.fx, fy = q.fy, gu = q.gu, gv = q.gv;
@@ -1127,9 +855,6 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
         }
     };
     auto consume2 = [&](const Pre2& q) {
-#ifdef MI_EMU_LIN48
-        asm volatile("" : : "v"(q.eA1), "v"(q.eA2), "v"(q.eB1), "v"(q.eB2));
-#endif
         const int i0 = q.i0, i1 = q.i1;
         const f2 fx = q.fx, fy = q.fy, gu = q.gu, gv = q.gv;
         const f2 fxy = fx * fy, gm = gv * fx + gu * fy;
@@ -1194,81 +919,9 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
         /* a row of the window per gather round (5 x 5: its five footprint records are neighbours in memory, 1-2
          * cache lines fetched once, five gathers in flight).  One sample at a time: in this layout the packed form measured
          * SLOWER (profiles/r5_ab_experiments.txt P: three wavefronts per SIMD already fill the issue slots, a packed
-         * instruction costs more than half of two plain ones, and the register pairs spill) */
-#ifdef MI_TOUCH_ROWS
-        /* experiment: the cache lines of the window's LATER rows are asked for before the first row is sampled -- one 4-byte load at
-         * the middle sample of each of those rows, its value thrown away at the end of the pass: the rows' own 16-byte gathers then
-         * find their lines on the way or there.  (What the throughput layout waits for, r6_ab_experiments.txt H: neither its VALU
-         * instructions nor the LDS -- 24 more of the one, 6 more look-ups of the other per sample cost nothing / 5 % -- but the
-         * slowest line of every row's gathers.) */
-        uint32_t touch[MI_FW];
-        touch[0] = 0u;
-#pragma unroll
-        for (int row = 1; row < MI_FW; ++row) {
-            const int i = row * MI_FW + MI_HALF;
-            const float fj = (float)(row - MI_HALF);
-            const float lam = (ps.depth + fj * ps.dzJ) * geo[i];
-            const float vx = nv.ax + fj * nv.dx, vy = nv.ay + fj * nv.dy, vz = nv.az + fj * nv.dz;
-            const float iz = fast_rcp(nv.sz + lam * vz);
-            const float uc = __builtin_amdgcn_fmed3f((nv.sx + lam * vx) * iz - 0.5f, kLo, wlim), vc = __builtin_amdgcn_fmed3f((nv.sy + lam * vy) * iz - 0.5f, kLo, hlim);
-            touch[row] = GU(nv.img + MI_QUAD_WORDS * (size_t)(__umul24((unsigned)vc, (unsigned)nv.w) + (unsigned)uc));
-        }
-#endif
-#ifdef MI_ROW2
-        /* experiment: the gathers of the NEXT row are issued before this row's samples are consumed (ten in flight instead of five;
-         * needs the registers of two wavefronts per SIMD: -DMI_WAVES_PER_SIMD=2) */
-        {
-            Pre qa[MI_FW], qb[MI_FW];
-#pragma unroll
-            for (int k = 0; k < MI_FW; ++k) qa[k] = geom(k);
-#pragma unroll 1
-            for (int row = 0; row < MI_FW; row += 2) {
-                if (row + 1 < MI_FW) {
-#pragma unroll
-                    for (int k = 0; k < MI_FW; ++k) qb[k] = geom((row + 1) * MI_FW + k);
-                }
-#pragma unroll
-                for (int k = 0; k < MI_FW; ++k) consume(qa[k]);
-                if (row + 2 < MI_FW) {
-#pragma unroll
-                    for (int k = 0; k < MI_FW; ++k) qa[k] = geom((row + 2) * MI_FW + k);
-                }
-                if (row + 1 < MI_FW) {
-#pragma unroll
-                    for (int k = 0; k < MI_FW; ++k) consume(qb[k]);
-                }
-            }
-        }
-#else
-        bool on_window = false;
-#ifdef MI_LDS_WINDOW
-        if constexpr (WIN) {
-            const bool ok_in = ok;
-            on_window = window_build(ps, nv, geo, (int)(threadIdx.x & 63u), win);
-            if (on_window) {
-#pragma unroll 1
-                for (int row = 0; row < MI_FW; ++row) {
-                    Pre q[MI_FW];
-#pragma unroll
-                    for (int k = 0; k < MI_FW; ++k) q[k] = geom_w(row * MI_FW + k, std::true_type{});
-#pragma unroll
-                    for (int k = 0; k < MI_FW; ++k) consume(q[k]);
-                }
-                if (__ballot(win_mx > win.limx || win_my > win.limy) != 0ull) {
-                    /* a sample outside its box (its texels were read from the box's edge): the pass is redone on the global gathers */
-                    on_window = false; ok = ok_in;
-                    if ((int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(true)) - 1) atomicAdd(&g_wstat[1], 1u);
-                    Pa0 = Pa1 = Pa2 = Paa0 = Paa1 = Paa2 = Pba0 = Pba1 = Pba2 = sp2(0.f);
-                    Pdr0 = Pdr1 = Pdr2 = Pdn0 = Pdn1 = Pdn2 = Pdd0 = Pdd1 = Pdd2 = sp2(0.f);
-                    Pnum = Pden = sp2(0.f);
-                    A00 = A01 = A02 = A11 = A12 = A22 = B0 = B1 = B2 = 0;
-                }
-            }
-            const unsigned long long actw = __ballot(true);
-            if (on_window && (int)(threadIdx.x & 63u) == __ffsll((long long)actw) - 1) atomicAdd(&g_wstat[0], 1u);
-        }
-#endif
-        if (!on_window) {
+         * instruction costs more than half of two plain ones, and the register pairs spill).  Measured against this loop and
+         * not adopted (profiles/r6_ab_experiments.txt I, L): the next row's gathers issued a row ahead, the later rows' cache
+         * lines touched before the first row, and the footprints staged through LDS windows. */
 #pragma unroll 1
         for (int row = 0; row < MI_FW; ++row) {
             Pre q[MI_FW];
@@ -1277,12 +930,6 @@ __device__ __forceinline__ bool sample_pass(const PatchState& ps, const NView& n
 #pragma unroll
             for (int k = 0; k < MI_FW; ++k) consume(q[k]);
         }
-        }
-#endif
-#ifdef MI_TOUCH_ROWS
-#pragma unroll
-        for (int row = 1; row < MI_FW; ++row) asm volatile("" : : "v"(touch[row]));
-#endif
     } else {
         constexpr int NP = NITER / 2;
         Pre2 q[NP > 0 ? NP : 1];
@@ -1606,15 +1253,12 @@ __device__ __forceinline__ bool view_prepare(const PatchState& ps, ViewC& vc, co
         premultiply(nv, Lv.ax, Lv.ay, Lv.cx, Lv.cy);
         nv.w = Lv.w; nv.h = Lv.h;
         nv.img = DV->quad + MI_QUAD_WORDS * (size_t)Lv.tex_off;
-#ifdef MI_LDS_WINDOW
-        nv.raw = DV->img + Lv.tex_off;
-#endif
     }
     return true;
 }
 
 /* One fused pass of my view at the current state; sets ps.ncc (getFastNCC).  Returns success[v]. */
-template <int MODE, class L, bool WIN = false>
+template <int MODE, class L>
 __device__ __forceinline__ bool run_pass(PatchState& ps, ViewC& vc, const DevView* views, const float* s_lut, const float* geo,
                                          const float* mcol, ColorSums& S, GNSums& gn, bool count_color, int sub) {
     bool okv = true;
@@ -1625,7 +1269,7 @@ __device__ __forceinline__ bool run_pass(PatchState& ps, ViewC& vc, const DevVie
     if (ps.sel >= 0) {
         okv = view_prepare(ps, vc, views);
         TSTAMP(52);
-        if (okv) okv = sample_pass<MODE, L, WIN>(ps, vc.nv, s_lut, geo, mcol, S, gn, nullptr, nullptr, sub);
+        if (okv) okv = sample_pass<MODE, L>(ps, vc.nv, s_lut, geo, mcol, S, gn, nullptr, nullptr, sub);
         ps.n_pass++;
         if (okv && MODE != PASS_DEPTH_FIXED_NC) {
             ps.ncc = ncc_from_sums(ps, S);
@@ -1850,19 +1494,14 @@ __device__ __forceinline__ bool run_turn(Run& R, const DevSettings& st, const De
     }
     bool okv;
     TSTAMP(20 + R.need);
-#ifdef MI_LDS_WINDOW
-    constexpr bool WIN = FAST && !L::LAT && L::NV == 4 && MI_FW == 5;      /* the first attempts of the large rounds (see g_win) */
-#else
-    constexpr bool WIN = false;
-#endif
-    if (R.need == PASS_DEPTH) okv = run_pass<PASS_DEPTH, L, WIN>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
+    if (R.need == PASS_DEPTH) okv = run_pass<PASS_DEPTH, L>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
     /* (the passes behind the depth-only steps of iterations 1..3: nobody asks for their NCC -- the reference's main loop, which
      * does, starts at iteration 4, patch_optimization.cc:177-192 --, so they carry no colour sums) */
     else if (R.need == PASS_DEPTH_FIXED && R.ctx == CTX_FIRST4 && !R.count_color)
-        okv = run_pass<PASS_DEPTH_FIXED_NC, L, WIN>(ps, R.vc, views, s_lut, geo, mcol, S, gn, false, sub);
-    else if (R.need == PASS_DEPTH_FIXED) okv = run_pass<PASS_DEPTH_FIXED, L, WIN>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
-    else if (R.need == PASS_NORMAL) okv = run_pass<PASS_NORMAL, L, WIN>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
-    else okv = run_pass<PASS_COLOR, L, WIN>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
+        okv = run_pass<PASS_DEPTH_FIXED_NC, L>(ps, R.vc, views, s_lut, geo, mcol, S, gn, false, sub);
+    else if (R.need == PASS_DEPTH_FIXED) okv = run_pass<PASS_DEPTH_FIXED, L>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
+    else if (R.need == PASS_NORMAL) okv = run_pass<PASS_NORMAL, L>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
+    else okv = run_pass<PASS_COLOR, L>(ps, R.vc, views, s_lut, geo, mcol, S, gn, R.count_color, sub);
     TSTAMP(30);
     /* ---- finish what led to this pass */
     if (R.ctx == CTX_CTOR || R.ctx == CTX_REPLACED) {
@@ -2400,9 +2039,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu((L::LAT ? 
 #ifdef MI_ACTIVITY
     if (lane < 2) g_act[lane] = 0;
 #endif
-#ifdef MI_LDS_WINDOW
-    if (FAST && !L::LAT && L::NV == 4 && lane < 4) g_wstat[lane] = 0;
-#endif
     __syncthreads();
     /* (DevCounters::clk_shader / clk_real: the shader clock this launch runs at, sampled by every 1024th wavefront) */
     const bool clk_probe = (blockIdx.x & 1023u) == 0u;
@@ -2455,14 +2091,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu((L::LAT ? 
         const unsigned long long ds = (unsigned long long)clock64() - clk_s0, dr = (unsigned long long)wall_clock64() - clk_r0;
         if (dr > 100ull) { atomicAdd(&a.counters->clk_shader, ds); atomicAdd(&a.counters->clk_real, dr); }   /* (wavefronts that found no work: too short to say anything) */
     }
-#ifdef MI_LDS_WINDOW
-    if constexpr (FAST && !L::LAT && L::NV == 4) {
-        /* (wavefront-passes on LDS windows / on global gathers, reported as mi_dmrecon_stats::n_patch_turns / n_wave_turns) */
-        __syncthreads();
-        if (lane == 0) { atomicAdd(&a.counters->n_stage, (unsigned long long)g_wstat[0] | ((unsigned long long)g_wstat[1] << 32));
-                         atomicAdd(&a.counters->n_gather_pass, (unsigned long long)g_wstat[2] | ((unsigned long long)g_wstat[3] << 32)); }
-    }
-#endif
 #ifdef MI_ACTIVITY
     __syncthreads();
     if (lane == 0 && !L::LAT) { atomicAdd(&a.counters->n_stage, (unsigned long long)g_act[0]); atomicAdd(&a.counters->n_gather_pass, (unsigned long long)g_act[1] * L::PATCHES); }
@@ -3487,23 +3115,17 @@ __global__ __launch_bounds__(256) void k_generate(SweepArgs a) {
     /* The stamps of the tile and a one-pixel rim, once, through LDS: a row of 66 stamps per load instruction of the workgroup --
      * nine coalesced loads per lane instead of four scattered ones per pixel (32 per lane): the kernel is bound by the NUMBER of
      * its load instructions (0.48 of a step's 12 ms; a bit per pixel in front of the same four loads made it slower,
-     * profiles/r6_ab_experiments.txt M), and the own confidence is only read where a neighbour's stamp says so.  Outside the
+     * profiles/r6_ab_experiments.txt M, N), and the own confidence is only read where a neighbour's stamp says so.  Outside the
      * image: -1, the stamp of a pixel never written. */
     constexpr int SW = MI_GEN_TILE_W + 2, SH = MI_GEN_TILE_H + 2;
     __shared__ int s_upd[SH * SW];
     static_assert(SW == 66 && SH * SW <= 65536 / 993 * 66, "i / 66 below is (i * 993) >> 16: exact for i < 4356");
-#ifndef MI_GEN_GLOBAL_STAMPS           /* (-DMI_GEN_GLOBAL_STAMPS: the stamps straight from memory, as until round 6 -- the A/B build) */
     for (int i = (int)threadIdx.x; i < SH * SW; i += 256) {
         const int r = (i * 993) >> 16, c = i - r * SW;
         const int y = ty0 - 1 + r, x = tx0 - 1 + c;
         s_upd[i] = (y >= 0 && y < H && x >= 0 && x < W) ? job->upd[(size_t)y * W + x] : -1;
     }
     __syncthreads();
-#define MI_STAMP(si, gi) s_upd[si]
-#else
-    (void)s_upd;
-#define MI_STAMP(si, gi) job->upd[gi]
-#endif
     unsigned hits = 0;                       /* bit t = my pixel of sub-tile t is a hit */
     unsigned before[GEN_PER_THREAD];         /* hits of lower lanes of my wave in trip t */
     unsigned wave_total = 0;
@@ -3524,11 +3146,11 @@ __global__ __launch_bounds__(256) void k_generate(SweepArgs a) {
             const int nb[4] = {pix - 1, pix + 1, pix - W, pix + W};
             const int sc = (wave * 8 + ly + 1) * SW + (t * 8 + lx + 1);                   /* my pixel in s_upd */
             const int snb[4] = {sc - 1, sc + 1, sc - SW, sc + SW};
-            if (a.self_round) { if (MI_STAMP(sc, pix) == a.round - 1) { any = true; cnt = 1; } }
+            if (a.self_round) { if (s_upd[sc] == a.round - 1) { any = true; cnt = 1; } }
             else {
                 unsigned fresh = 0;                                                        /* bit k: neighbour k was written last round */
 #pragma unroll
-                for (int k = 0; k < 4; ++k) fresh |= (MI_STAMP(snb[k], nb[k]) == a.round - 1 ? 1u : 0u) << k;
+                for (int k = 0; k < 4; ++k) fresh |= (s_upd[snb[k]] == a.round - 1 ? 1u : 0u) << k;
                 if (fresh) {
                     const float own = job->conf[pix];
 #pragma unroll
@@ -3882,16 +3504,7 @@ __global__ __launch_bounds__(256) void k_quadify(const uint32_t* __restrict__ sr
     const int x1 = x + 1 < w ? x + 1 : x, y1 = y + 1 < h ? y + 1 : y;
     u32x4 o;
     o.x = src[y * w + x]; o.y = src[y * w + x1]; o.z = src[y1 * w + x]; o.w = src[y1 * w + x1];
-#ifdef MI_TILED_QUADS
-    dst[(((unsigned)(y >> 3) * ((unsigned)(w + 7) >> 3) + (unsigned)(x >> 3)) << 6) | ((unsigned)(y & 7) << 3) | (unsigned)(x & 7)] = o;
-#elif defined(MI_PAIR_RECORDS)
     reinterpret_cast<uint32_t*>(dst)[2 * (size_t)i] = o.x; reinterpret_cast<uint32_t*>(dst)[2 * (size_t)i + 1] = o.z;   /* (x, y), (x, y + 1) */
-#else
-    dst[(size_t)i * (MI_QUAD_WORDS / 4)] = o;
-#if MI_QUAD_WORDS > 4
-    dst[(size_t)i * (MI_QUAD_WORDS / 4) + 1] = o; dst[(size_t)i * (MI_QUAD_WORDS / 4) + 2] = o;
-#endif
-#endif
 }
 
 #if MI_FW == 5
@@ -4221,7 +3834,6 @@ void mi_launch_unpack_jobs(hipStream_t s, const uint32_t* packed, unsigned words
     hipLaunchKernelGGL(k_unpack_jobs, dim3(words_per_job > 768u ? 4u : (words_per_job + 255u) / 256u, (unsigned)n_jobs), dim3(256), 0, s,
                        packed, words_per_job, reinterpret_cast<uint32_t*>(jobs), (unsigned)(sizeof(DevJob) / 4));
 }
-unsigned mi_quad_words(void) { return MI_QUAD_WORDS; }      /* words per footprint record of this build (the host sizes the views by it) */
 void mi_launch_quadify(hipStream_t s, const uint32_t* src, uint32_t* dst, int w, int h) {
     hipLaunchKernelGGL(k_quadify, dim3((w * h + 255) / 256), dim3(256), 0, s, src, (u32x4*)dst, w, h);
 }

@@ -1540,9 +1540,9 @@ static size_t host_view_set_camera(HostView& v, const mi_dmrecon_camera* cam, in
     HostLevel l0; l0.w = cw; l0.h = ch; l0.tex_off = 0;
     calibration(pc, (float)cw, (float)ch, l0.proj, l0.invproj);
     v.levels.push_back(l0);
-    /* (a level's slot holds its texels row by row AND -- four times that, behind the levels -- its footprint records; the slot
-     * is padded to whole 8 x 8 tiles so that a block-linear arrangement of the records fits as well: the -DMI_TILED_QUADS
-     * experiment of the device code.  < 1 % of a view's memory.) */
+    /* (a level's slot holds its texels row by row AND -- MI_QUAD_WORDS times that, behind the levels -- its footprint elements.
+     * The slot is padded to whole 8 x 8 tiles, < 1 % of a view's memory: nothing needs the padding any more, but it decides
+     * every level's tex_off, and with the addresses the cache behaviour of the sampler -- it stays as measured.) */
     auto slot = [](int w, int h) { return (size_t)((w + 7) & ~7) * (size_t)((h + 7) & ~7); };
     off += slot(cw, ch);
     while (std::min(cw, ch) >= 30 && v.levels.size() < MI_MAX_LEVELS) {
@@ -1580,7 +1580,7 @@ static int set_view_impl(mi_dmrecon_ctx* c, int32_t view_id, const mi_dmrecon_ca
      * sample's 2 x 2 footprint is one 16-byte gather over two of them; the last gather of the last level ends 8 bytes past its
      * elements, hence the pad): 4 + 8 bytes per texel */
     v.quad_off = (off + 3) & ~(size_t)3;
-    HIP_TRY(hipMalloc((void**)&v.d_img, (v.quad_off + (size_t)mi_quad_words() * off + 4) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&v.d_img, (v.quad_off + (size_t)MI_QUAD_WORDS * off + 4) * sizeof(uint32_t)));
     /* ensureImages, image_pyramid.cc:55-95: upload, strip alpha / expand grey, then the Gaussian levels */
     const size_t nbytes = (size_t)width * height * channels;
     /* two device staging buffers used alternately: the copy of view i+1 (from pinned memory) can start
@@ -1599,7 +1599,7 @@ static int set_view_impl(mi_dmrecon_ctx* c, int32_t view_id, const mi_dmrecon_ca
     }
     for (size_t l = 0; l < v.levels.size(); ++l) {
         HostLevel const& a = v.levels[l];
-        mi_launch_quadify(c->stream, v.d_img + a.tex_off, v.d_img + v.quad_off + (size_t)mi_quad_words() * (size_t)a.tex_off, a.w, a.h);
+        mi_launch_quadify(c->stream, v.d_img + a.tex_off, v.d_img + v.quad_off + (size_t)MI_QUAD_WORDS * (size_t)a.tex_off, a.w, a.h);
     }
     HIP_TRY(hipGetLastError());
     if (!async) HIP_TRY(wait_stream(c->stream));

@@ -14,6 +14,7 @@
 #define MI_MAX_LOCAL 16         /* local views per patch (Settings::nrReconNeighbors): four, eight or sixteen view slots */
 #define MI_MAX_FW 7         /* filter widths 3, 5, 7: the device code is compiled once per width (dmrecon_device.hip) */
 #define MI_PATCHES_PER_WAVE 16
+#define MI_QUAD_WORDS 2         /* 32-bit words per footprint element (DevView::quad): a column pair of RGBA8 texels */
 #define MI_VIEW_NONE 0xFFu
 #define MI_MAX_ROUNDS 8192      /* per-round work counters kept on the device */
 
@@ -34,7 +35,7 @@ struct DevView {
     const uint32_t* img;     /* all levels back to back, RGBA8 (A unused), row-major */
     const uint32_t* quad;    /* same levels as footprint elements: element (x, y) = texels (x,y) (x,y+1), 8 bytes, edge-clamped --
                               * the whole bilinear footprint of a sample = elements x, x + 1 of row y in ONE 16-byte gather
-                              * (mi_quad_words() words per element: 2; the 16-byte records of rounds 2-5 with -DMI_QUAD_RECORDS) */
+                              * (MI_QUAD_WORDS words per element) */
     DevLevel lv[MI_MAX_LEVELS];
 };
 

@@ -180,6 +180,32 @@ def test_every_run_time_switch_is_documented():
     assert not extra, sorted(extra)
 
 
+def test_every_build_switch_is_documented():
+    """Every MI_* name that a preprocessor conditional of the kernel sources tests is a row of DESIGN.md's table "Build switches
+    of the kernel source", and the table names no switch that the sources no longer test (include guards and arithmetic on the
+    filter width, `#if MI_FW == 5`, aside)."""
+    csrc = os.path.join(ROOT, "mve_amd", "csrc")
+    tested = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        for line in open(os.path.join(csrc, f)):
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+            if not m:
+                continue
+            expr = re.sub(r"/\*.*?(\*/|$)|//.*", "", m.group(2))
+            names = set(re.findall(r"\bMI_\w+", expr))
+            if m.group(1) in ("if", "elif") and not re.search(r"defined\s*\(?\s*MI_FW\b", expr):
+                names.discard("MI_FW")
+            tested |= {n for n in names if not n.endswith("_H")}
+    doc = open(os.path.join(ROOT, "DESIGN.md")).read()
+    at = doc.index("Build switches of the kernel source")
+    rows = re.match(r"(?:[^\n]*\n)*?((?:\|[^\n]*\n)+)", doc[at:]).group(1)
+    named = set(re.findall(r"^\|\s*`(MI_\w+)`", rows, re.M))
+    assert len(tested) >= 8
+    assert tested == named, (sorted(tested - named), sorted(named - tested))
+
+
 def test_bench_call_plan():
     """bench.py: how K timed steps become library calls (pure host logic)."""
     import importlib.util

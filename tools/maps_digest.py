@@ -1,6 +1,5 @@
 """A digest of the maps of one call over all reference views of a config's scene (and of a merged batch of `copies` such
-calls' worth of views): two builds of the library give the same digests iff their maps are the same bits.  Prints one JSON object
-(with the window counters of a -DMI_LDS_WINDOW build: wavefront-passes on LDS windows / on global gathers).
+calls' worth of views): two builds of the library give the same digests iff their maps are the same bits.  Prints one JSON object.
 
     MI_DMRECON_LIB=build/libmi_dmrecon_<variant>.so python tools/maps_digest.py [CONFIG] [copies]      (GPU box)
 """
@@ -27,6 +26,5 @@ for label, views in (("one_call", list(range(p.n_views))), ("batch_x%d" % copies
                 h.update(np.ascontiguousarray(r[k]).tobytes())
     s = ctx.last_stats
     out[label] = {"sha256": h.hexdigest(), "n_patch": int(s.get("n_patch", 0)), "n_pass": int(s.get("n_pass", 0)),
-                  "window_passes": int(s.get("n_patch_turns", 0)), "gather_passes": int(s.get("n_wave_turns", 0)),
                   "ms_bulk_kernel": s.get("ms_bulk_kernel"), "filled": int(sum(int((r["depth"] > 0).sum()) for r in res[:p.n_views]))}
 print(json.dumps(out))
