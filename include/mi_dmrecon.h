@@ -369,6 +369,65 @@ int  mi_dmrecon_fssr_sample(mi_dmrecon_fssr* f, const mi_dmrecon_fssr_options* o
 /* Frees the device copy.  Destroy it before its context. */
 void mi_dmrecon_fssr_destroy(mi_dmrecon_fssr* f);
 
+/* ---- the stage before all of them: the pairwise descriptor matching of apps/sfmrecon -------------------------------- */
+
+/* sfm::ExhaustiveMatching (libs/sfm/exhaustive_matching.cc) over sfm::Matching::twoway_match (libs/sfm/matching.h:114-159)
+ * and sfm::NearestNeighbor<T>::find (libs/sfm/nearest_neighbor.cc:64-133, :218-272), for the two 8-bit descriptor types
+ * (DISCRETIZE_DESCRIPTORS 1, exhaustive_matching.h:21); NearestNeighbor<float> (:276-293) is not covered, sfmrecon never
+ * uses it.
+ *
+ * For a query q and a set B the reference visits <q, B_j> with j ascending, compares with `>=` twice and starts from
+ * (product 0, index 0) twice.  Without the loop: the top two, under the total order (inner product, then index, both
+ * descending), of the elements of B whose inner product is >= 0, padded with two dummies that rank below every real
+ * element and report product 0 and index 0.  Ties go to the larger index.  The library computes true 32-bit integer inner
+ * products.  The reference holds them in 16 bits: the results are the reference's for inputs whose inner products, between
+ * any two descriptors of a call, lie in 0 ... 65535 (SIFT) or -32768 ... 32767 (SURF) -- discretised unit-norm
+ * descriptors do -- and are unspecified against the reference outside that domain. */
+#define MI_DMRECON_MATCH_SIFT 0   /* 128 dims, unsigned: clamp(v, 0, 1) * 255, math::round (exhaustive_matching.cc:18-27) */
+#define MI_DMRECON_MATCH_SURF 1   /* 64 dims, signed: clamp(v, -1, 1) * 127, math::round (exhaustive_matching.cc:29-39) */
+#define MI_DMRECON_MATCH_F32 0    /* float descriptors, discretised by the library (on the device) */
+#define MI_DMRECON_MATCH_I16 1    /* the reference's in-memory form: uint16 / int16 holding 8-bit values (exhaustive_matching.h:47-48) */
+
+typedef struct mi_dmrecon_match mi_dmrecon_match;
+
+/* sfm::Matching::Options (matching.h:29-50) without the descriptor length, which the kind fixes. */
+typedef struct mi_dmrecon_match_options {
+    int32_t struct_size;            /* sizeof(mi_dmrecon_match_options), set by the caller */
+    float   lowe_ratio_threshold;
+    float   distance_threshold;
+} mi_dmrecon_match_options;
+
+/* One two-way match: the first n_a descriptors of set_a against the first n_b of set_b (the prefixes are what
+ * ExhaustiveMatching::pairwise_match_lowres takes, exhaustive_matching.cc:142-176). */
+typedef struct mi_dmrecon_match_job {
+    int32_t set_a, n_a, set_b, n_b;
+} mi_dmrecon_match_job;
+
+/* A matcher for n_sets descriptor sets (one per view) on the context's device; each set holds a SIFT and a SURF list. */
+int  mi_dmrecon_match_create(mi_dmrecon_ctx* ctx, int32_t n_sets, mi_dmrecon_match** out);
+
+/* ExhaustiveMatching::init_sift / init_surf (exhaustive_matching.cc:72-108): n descriptors of `kind` (n x 128 or n x 64
+ * values of `dtype`) become set `set`'s list of that kind, packed to bytes on the device; an earlier list is replaced.
+ * MI_DMRECON_EINVAL for: a set outside [0, n_sets); an unknown kind or dtype; a negative n; an I16 value outside 0 ... 255
+ * (SIFT) or -128 ... 127 (SURF).  Not to be called while mi_dmrecon_match_pairs runs on the same handle. */
+int  mi_dmrecon_match_set(mi_dmrecon_match* m, int32_t set, int32_t kind, int32_t dtype, int32_t n, const void* descriptors);
+
+/* Matching::twoway_match (matching.h:148-159) for n_jobs jobs on the lists of `kind`, in a fixed number of launches for
+ * the whole list.  matches_ab[j] (n_a entries) and matches_ba[j] (n_b entries) receive the RAW one-way results of
+ * Matching::oneway_match (matching.h:114-146; -1: no match), before Matching::remove_inconsistent_matches; the arrays and
+ * each of their pointers may be NULL.  n_consistent[j] (may be NULL) is Matching::count_consistent_matches of the two
+ * (matching.cc:38-47).  The tests are the reference's: d1 > distance_threshold^2 and d1 / d2 > lowe_ratio_threshold^2 in
+ * float, so 0 / 0 (NaN) is accepted.  A job with an empty side gives all -1 and launches nothing.
+ * MI_DMRECON_EINVAL for: a set outside [0, n_sets); n_a or n_b negative or greater than the set's list; an unknown kind;
+ * options that are NULL or whose struct_size is not set.
+ * May be called from several host threads on one handle at the same time (sfmrecon calls it from an OpenMP loop). */
+int  mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs,
+                            const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
+                            int32_t* n_consistent);
+
+/* Frees the sets, streams and result buffers.  Destroy it before its context. */
+void mi_dmrecon_match_destroy(mi_dmrecon_match* m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,11 @@ EXPORTS = [
     "mi_dmrecon_global_view_selection", "mi_dmrecon_reconstruct",
     "mi_dmrecon_patch_optimize", "mi_dmrecon_patch_eval", "mi_dmrecon_pointset",
     "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
+    "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
 ]
+
+MATCH_SIFT, MATCH_SURF = 0, 1      # MI_DMRECON_MATCH_SIFT / _SURF: 128 unsigned dims / 64 signed dims
+MATCH_F32, MATCH_I16 = 0, 1        # MI_DMRECON_MATCH_F32 / _I16
 
 
 class CCamera(ctypes.Structure):
@@ -79,6 +83,15 @@ class CFssrNode(ctypes.Structure):
 
 class CFssrOptions(ctypes.Structure):
     _fields_ = [("list_capacity", ctypes.c_int32)]
+
+
+class CMatchOptions(ctypes.Structure):
+    """mi_dmrecon_match_options = sfm::Matching::Options (libs/sfm/matching.h:29-50) without the descriptor length."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("lowe_ratio_threshold", ctypes.c_float), ("distance_threshold", ctypes.c_float)]
+
+
+class CMatchJob(ctypes.Structure):
+    _fields_ = [("set_a", ctypes.c_int32), ("n_a", ctypes.c_int32), ("set_b", ctypes.c_int32), ("n_b", ctypes.c_int32)]
 
 
 class CProgress(ctypes.Structure):
@@ -185,6 +198,12 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_fssr_sample.argtypes = [vp, ctypes.POINTER(CFssrOptions), i64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.mi_dmrecon_fssr_destroy.argtypes = [vp]
         L.mi_dmrecon_fssr_destroy.restype = None
+    if hasattr(L, "mi_dmrecon_match_create"):
+        L.mi_dmrecon_match_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
+        L.mi_dmrecon_match_set.argtypes = [vp, i32, i32, i32, i32, vp]
+        L.mi_dmrecon_match_pairs.argtypes = [vp, i32, ctypes.POINTER(CMatchOptions), i32, vp, vp, vp, vp]
+        L.mi_dmrecon_match_destroy.argtypes = [vp]
+        L.mi_dmrecon_match_destroy.restype = None
     _lib = L
     return L
 
@@ -611,6 +630,82 @@ class Context:
         Octree::influence_query visits them; ``nodes``: (N, 4) int32 rows first_child, first_sample, n_samples, 0 with
         the root first, or None for "no tree" (every sample is tested for every voxel)."""
         return FssrSampler(self, samples, nodes, root_center, root_size)
+
+
+    def match_open(self, n_sets: int) -> "Matcher":
+        """A matcher for ``n_sets`` descriptor sets on this context's device (mi_dmrecon_match_create)."""
+        return Matcher(self, n_sets)
+
+
+class Matcher:
+    """sfm::Matching::twoway_match (libs/sfm/matching.h:114-159) over descriptor sets that stay on the GPU as bytes; see
+    Context.match_open.  ``pairs`` may be called from several threads at once."""
+
+    def __init__(self, ctx: Context, n_sets: int):
+        self._L = ctx._L
+        self._ctx = ctx                 # the handle lives on the context's device
+        self._h = None
+        if not hasattr(self._L, "mi_dmrecon_match_create"):
+            raise RuntimeError("%s has no mi_dmrecon_match_* entry points: rebuild the library" % LIB_PATH)
+        h = ctypes.c_void_p()
+        rc = self._L.mi_dmrecon_match_create(ctx._h, int(n_sets), ctypes.byref(h))
+        if rc < 0:
+            _raise(rc)
+        self._h = h
+
+    def set(self, i: int, kind: int, descriptors) -> None:
+        """Set ``i``'s descriptors of ``kind`` (MATCH_SIFT: (n, 128), MATCH_SURF: (n, 64)): float32, discretised by the
+        library as ExhaustiveMatching::init does (libs/sfm/exhaustive_matching.cc:18-39), or the reference's discretised
+        form, uint16 (SIFT) / int16 (SURF)."""
+        if self._h is None:
+            raise RuntimeError("the matcher is closed")
+        d = np.asarray(descriptors)
+        dims = {MATCH_SIFT: 128, MATCH_SURF: 64}.get(kind)
+        if dims is None:
+            raise ValueError("unknown descriptor kind %r" % (kind,))
+        if d.ndim != 2 or d.shape[1] != dims:
+            raise ValueError("descriptors: (n, %d) expected" % dims)
+        if d.dtype == np.float32:
+            dtype = MATCH_F32
+        elif d.dtype == (np.uint16 if kind == MATCH_SIFT else np.int16):
+            dtype = MATCH_I16
+        else:
+            raise ValueError("descriptors: float32 or %s expected" % ("uint16" if kind == MATCH_SIFT else "int16"))
+        d = np.ascontiguousarray(d)
+        rc = self._L.mi_dmrecon_match_set(self._h, int(i), int(kind), dtype, len(d), _ptr(d) if len(d) else None)
+        if rc < 0:
+            _raise(rc)
+
+    def pairs(self, kind: int, jobs, lowe_ratio: float, distance: float):
+        """One two-way match per job (set_a, n_a, set_b, n_b), all in one call: a list of (matches_ab [n_a], matches_ba [n_b],
+        n_consistent) with the RAW one-way results (-1: no match) and Matching::count_consistent_matches of the two."""
+        if self._h is None:
+            raise RuntimeError("the matcher is closed")
+        jobs = [tuple(int(v) for v in j) for j in jobs]
+        n = len(jobs)
+        cj = (CMatchJob * max(n, 1))(*[CMatchJob(*j) for j in jobs])
+        ab = [np.full(max(j[1], 0), -1, np.int32) for j in jobs]
+        ba = [np.full(max(j[3], 0), -1, np.int32) for j in jobs]
+        pab = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in ab])
+        pba = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in ba])
+        cnt = np.zeros(max(n, 1), np.int32)
+        opt = CMatchOptions(ctypes.sizeof(CMatchOptions), lowe_ratio, distance)
+        rc = self._L.mi_dmrecon_match_pairs(self._h, int(kind), ctypes.byref(opt), n, ctypes.cast(cj, ctypes.c_void_p),
+                                            ctypes.cast(pab, ctypes.c_void_p), ctypes.cast(pba, ctypes.c_void_p), _ptr(cnt))
+        if rc < 0:
+            _raise(rc)
+        return [(ab[k], ba[k], int(cnt[k])) for k in range(n)]
+
+    def close(self):
+        if self._h is not None:
+            self._L.mi_dmrecon_match_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FssrSampler:
