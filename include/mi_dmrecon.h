@@ -419,7 +419,9 @@ int  mi_dmrecon_match_set(mi_dmrecon_match* m, int32_t set, int32_t kind, int32_
  * (matching.cc:38-47).  The tests are the reference's: d1 > distance_threshold^2 and d1 / d2 > lowe_ratio_threshold^2 in
  * float, so 0 / 0 (NaN) is accepted.  A job with an empty side gives all -1 and launches nothing.
  * MI_DMRECON_EINVAL for: a set outside [0, n_sets); n_a or n_b negative or greater than the set's list; an unknown kind;
- * options that are NULL or whose struct_size is not set.
+ * options that are NULL or whose struct_size is not set; a single job of more than 2^24 - 1 tiles of 64 x 2048
+ * (ceil(n_a / 64) * ceil(n_b / 2048) workgroups: more than one launch holds) -- the message names the job and the count,
+ * nothing has been allocated or launched, and the handle stays usable.
  * May be called from several host threads on one handle at the same time (sfmrecon calls it from an OpenMP loop). */
 int  mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs,
                             const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,

@@ -1,9 +1,10 @@
 /*
  * mi_dmrecon_debug.h -- test and development hooks of libmi_dmrecon.so.
  *
- * NOT part of the drop-in boundary (include/mi_dmrecon.h is; nothing here replaces anything of the reference): these six
+ * NOT part of the drop-in boundary (include/mi_dmrecon.h is; nothing here replaces anything of the reference): these nine
  * entry points exist for tests/ and tools/ -- fault injection, the host-only halves of the planning (so that they can be
- * checked against the oracle without a GPU), pool introspection and the probe buffer of -DMI_PROBE builds.  They are
+ * checked against the oracle without a GPU), pool introspection, the probe buffer of -DMI_PROBE builds, and the stored
+ * bytes and the batching of the descriptor matching.  They are
  * declared here so that the library exports nothing that no header declares (the link uses a version script: only
  * mi_dmrecon_* symbols leave the library, tests/test_abi_and_host.py checks that every one of them is declared in one of
  * the two headers).  A production caller never needs them; they may change without notice.
@@ -48,6 +49,22 @@ int mi_dmrecon_debug_region_mark(mi_dmrecon_ctx* ctx, int tag);
 /* The debug buffer of -DMI_PROBE builds (tools/patch_probe.py): the first call allocates n 8-byte words on the device; later
  * calls copy up to n words out and clear the buffer. */
 int mi_dmrecon_debug_buffer(unsigned long long* out, int n);
+
+/* Set `set`'s list of `kind` as the device holds it: n x 128 / n x 64 packed bytes (SIFT biased by -128) to bytes_out and the n
+ * `off` words (128 * the sum of a row's stored bytes + 2^20; 0 for SURF) to off_out; either may be NULL.  Returns n. */
+int mi_dmrecon_debug_match_get(mi_dmrecon_match* m, int32_t set, int32_t kind, int8_t* bytes_out, int32_t* off_out);
+
+/* Replaces the two limits of a batch of mi_dmrecon_match_pairs (rows + columns, workgroups) for the calls that follow, in the
+ * whole process; 0 restores a default.  MI_DMRECON_EINVAL for more workgroups than a launch holds.  Not to be called while
+ * mi_dmrecon_match_pairs runs. */
+int mi_dmrecon_debug_match_limits(long long entries, long long blocks);
+
+/* The batches mi_dmrecon_match_pairs makes of n_jobs jobs of n_a[j] x n_b[j] descriptors under the two limits (0: the one in
+ * force): per job its batch (-1: an empty side, it runs nowhere), its first workgroup and its workgroups per strip of rows
+ * in that batch's grid, and its first entry in that batch's buffers; each array may be NULL.  Returns the number of batches,
+ * or MI_DMRECON_EINVAL for a job that needs more workgroups than the limit.  The function the call itself runs on; needs no GPU. */
+int mi_dmrecon_debug_match_plan(int32_t n_jobs, const int32_t* n_a, const int32_t* n_b, long long entries, long long blocks,
+                                int32_t* batch_out, int32_t* block0_out, int32_t* col_chunks_out, int64_t* entry0_out);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,13 @@ EXPORTS = [
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
 ]
 
+# the test hooks of include/mi_dmrecon_debug.h (EXPORTS is the drop-in boundary, include/mi_dmrecon.h, alone)
+DEBUG_EXPORTS = [
+    "mi_dmrecon_debug_inject_footprint", "mi_dmrecon_debug_front_teams", "mi_dmrecon_debug_plan_views_host",
+    "mi_dmrecon_debug_scratch_sets", "mi_dmrecon_debug_region_mark", "mi_dmrecon_debug_buffer",
+    "mi_dmrecon_debug_match_get", "mi_dmrecon_debug_match_limits", "mi_dmrecon_debug_match_plan",
+]
+
 MATCH_SIFT, MATCH_SURF = 0, 1      # MI_DMRECON_MATCH_SIFT / _SURF: 128 unsigned dims / 64 signed dims
 MATCH_F32, MATCH_I16 = 0, 1        # MI_DMRECON_MATCH_F32 / _I16
 
@@ -204,6 +211,11 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_match_pairs.argtypes = [vp, i32, ctypes.POINTER(CMatchOptions), i32, vp, vp, vp, vp]
         L.mi_dmrecon_match_destroy.argtypes = [vp]
         L.mi_dmrecon_match_destroy.restype = None
+    if hasattr(L, "mi_dmrecon_debug_match_get"):                                                             # test hooks
+        ll = ctypes.c_longlong
+        L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
+        L.mi_dmrecon_debug_match_limits.argtypes = [ll, ll]
+        L.mi_dmrecon_debug_match_plan.argtypes = [i32, vp, vp, ll, ll, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -273,6 +285,32 @@ def plan_views_host(scene: "SceneData", st: "Settings", ref_view: int, tables: b
     if seeds:
         return ids, ms.value, (sxy[:ns.value].copy(), sd[:ns.value].copy())
     return ids, ms.value
+
+
+def match_limits(entries: int = 0, blocks: int = 0) -> None:
+    """Test hook: the two limits of a batch of Matcher.pairs (rows + columns, workgroups) for the calls that follow, in the
+    whole process; 0 restores a default.  Not while a ``pairs`` runs."""
+    rc = load_library().mi_dmrecon_debug_match_limits(int(entries), int(blocks))
+    if rc < 0:
+        _raise(rc)
+
+
+def match_plan(sizes, entries: int = 0, blocks: int = 0):
+    """Test hook: the batches Matcher.pairs makes of jobs of ``sizes`` = [(n_a, n_b)] under the two limits (0: the one in
+    force); the function the call itself runs on, no GPU needed.  Returns (number of batches, batch [n] with -1 for a job
+    with an empty side, block0 [n], col_chunks [n], entry0 [n]); ValueError for a job that needs more workgroups than
+    ``blocks``."""
+    n = len(sizes)
+    na = np.ascontiguousarray([s[0] for s in sizes], np.int32).reshape(n)
+    nb = np.ascontiguousarray([s[1] for s in sizes], np.int32).reshape(n)
+    batch, block0, chunks = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    entry0 = np.zeros(n, np.int64)
+    rc = load_library().mi_dmrecon_debug_match_plan(n, _ptr(na) if n else None, _ptr(nb) if n else None, int(entries), int(blocks),
+                                                    _ptr(batch) if n else None, _ptr(block0) if n else None,
+                                                    _ptr(chunks) if n else None, _ptr(entry0) if n else None)
+    if rc < 0:
+        _raise(rc)
+    return rc, batch, block0, chunks, entry0
 
 
 def device_count() -> int:
@@ -695,6 +733,22 @@ class Matcher:
         if rc < 0:
             _raise(rc)
         return [(ab[k], ba[k], int(cnt[k])) for k in range(n)]
+
+    def debug_get(self, i: int, kind: int):
+        """Test hook: set ``i``'s list of ``kind`` as the device holds it: (bytes int8 (n, 128) / (n, 64), SIFT biased by
+        -128; off int32 [n])."""
+        if self._h is None:
+            raise RuntimeError("the matcher is closed")
+        dims = {MATCH_SIFT: 128, MATCH_SURF: 64}[kind]
+        n = self._L.mi_dmrecon_debug_match_get(self._h, int(i), int(kind), None, None)
+        if n < 0:
+            _raise(n)
+        b, off = np.zeros((n, dims), np.int8), np.zeros(n, np.int32)
+        if n:
+            rc = self._L.mi_dmrecon_debug_match_get(self._h, int(i), int(kind), _ptr(b), _ptr(off))
+            if rc < 0:
+                _raise(rc)
+        return b, off
 
     def close(self):
         if self._h is not None:

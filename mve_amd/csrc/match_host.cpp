@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mi_dmrecon.h"
+#include "../../include/mi_dmrecon_debug.h"
 #include "match_device.h"
 
 /* dmrecon_host.cpp: the thread-local error message and the context's device (not exported, exports.map) */
@@ -26,7 +28,10 @@ namespace {
 
 #define MATCH_SLOTS 4                        /* calls of mi_dmrecon_match_pairs in flight on one handle */
 #define MATCH_BATCH_ENTRIES (1ll << 26)      /* rows + columns per pair of launches (16 bytes of keys each) */
-#define MATCH_BATCH_BLOCKS (1ll << 30)
+#define MATCH_BATCH_BLOCKS ((1ll << 24) - 1)  /* workgroups per launch: HIP wants gridDim.x * blockDim.x < 2^32, the workgroups have 256 threads */
+
+/* the limits in force: the two above unless mi_dmrecon_debug_match_limits replaced them */
+std::atomic<long long> g_batch_entries(MATCH_BATCH_ENTRIES), g_batch_blocks(MATCH_BATCH_BLOCKS);
 
 struct MatchSet {
     int32_t n = 0;
@@ -226,6 +231,35 @@ int grow(MatchSlot& s, size_t n_jobs, size_t n_entries) {
     return 0;
 }
 
+/* Where a job runs: its batch (-1: it has an empty side and runs nowhere) and its place in that batch's grid and buffers. */
+struct MatchPlan {
+    int32_t batch, block0, col_chunks;
+    int64_t entry0;
+};
+
+long long job_chunks(int32_t n_b) { return ((long long)n_b + MATCH_CHUNK - 1) / MATCH_CHUNK; }
+long long job_blocks(int32_t n_a, int32_t n_b) { return (((long long)n_a + MATCH_STRIP - 1) / MATCH_STRIP) * job_chunks(n_b); }
+
+/* The batches of a job list: jobs in order, a new batch (one launch of each kernel, block0 and entry0 from 0 again) where
+ * the next job would take the batch past lim_blocks workgroups or lim_entries rows + columns.  A single job above
+ * lim_entries goes alone; one above lim_blocks fits no launch: MI_DMRECON_EINVAL.  Returns the number of batches. */
+int plan_batches(int32_t n_jobs, const int32_t* n_a, const int32_t* n_b, long long lim_entries, long long lim_blocks, MatchPlan* out) {
+    int32_t batch = -1;
+    long long blocks = 0, entries = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        MatchPlan& p = out[j];
+        p.batch = -1; p.block0 = 0; p.col_chunks = 0; p.entry0 = 0;
+        if (n_a[j] == 0 || n_b[j] == 0) continue;
+        const long long nb = job_blocks(n_a[j], n_b[j]), ne = (long long)n_a[j] + n_b[j];
+        if (nb > lim_blocks)
+            return failf(MI_DMRECON_EINVAL, "match: job %lld needs %lld workgroups, a launch holds %lld", j, nb, lim_blocks);
+        if (batch < 0 || blocks + nb > lim_blocks || entries + ne > lim_entries) { ++batch; blocks = 0; entries = 0; }
+        p.batch = batch; p.block0 = (int32_t)blocks; p.col_chunks = (int32_t)job_chunks(n_b[j]); p.entry0 = entries;
+        blocks += nb; entries += ne;
+    }
+    return batch + 1;
+}
+
 int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs, const mi_dmrecon_match_job* jobs,
                int32_t* const* matches_ab, int32_t* const* matches_ba, int32_t* n_consistent) {
     if (!m) return failf(MI_DMRECON_EINVAL, "match: null handle");
@@ -252,6 +286,15 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
     const float square_lowe_thres = opt->lowe_ratio_threshold * opt->lowe_ratio_threshold;
     const float square_dist_thres = opt->distance_threshold * opt->distance_threshold;
 
+    /* every batch is known, and a job no launch can hold refused, before anything is allocated or launched */
+    std::vector<MatchPlan> plan(n_jobs);
+    {
+        std::vector<int32_t> na(n_jobs), nb(n_jobs);
+        for (int32_t j = 0; j < n_jobs; ++j) { na[j] = jobs[j].n_a; nb[j] = jobs[j].n_b; }
+        const int n_batches = plan_batches(n_jobs, na.data(), nb.data(), g_batch_entries.load(), g_batch_blocks.load(), plan.data());
+        if (n_batches < 0) return n_batches;
+    }
+
     /* a job with an empty side: all -1, nothing launched (matching.h:121-124) */
     for (int32_t j = 0; j < n_jobs; ++j) {
         const mi_dmrecon_match_job& q = jobs[j];
@@ -267,22 +310,19 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
     std::vector<MatchJobDev> dev;
     std::vector<int32_t> which;
     int32_t j = 0;
-    while (j < n_jobs) {
+    for (int32_t batch = 0;; ++batch) {
         dev.clear(); which.clear();
         long long blocks = 0, entries = 0;
-        for (; j < n_jobs; ++j) {
+        for (; j < n_jobs && plan[j].batch <= batch; ++j) {
+            if (plan[j].batch < 0) continue;
             const mi_dmrecon_match_job& q = jobs[j];
-            if (q.n_a == 0 || q.n_b == 0) continue;
-            const long long chunks = (q.n_b + MATCH_CHUNK - 1) / MATCH_CHUNK;
-            const long long nb = (long long)((q.n_a + MATCH_STRIP - 1) / MATCH_STRIP) * chunks;
-            if (!dev.empty() && (blocks + nb > MATCH_BATCH_BLOCKS || entries + q.n_a + q.n_b > MATCH_BATCH_ENTRIES)) break;
             MatchJobDev d;
             d.a = sets[q.set_a].d_desc; d.off_a = sets[q.set_a].d_off;
             d.b = sets[q.set_b].d_desc; d.off_b = sets[q.set_b].d_off;
             d.n_a = q.n_a; d.n_b = q.n_b;
-            d.block0 = (int32_t)blocks; d.col_chunks = (int32_t)chunks; d.entry0 = entries;
+            d.block0 = plan[j].block0; d.col_chunks = plan[j].col_chunks; d.entry0 = plan[j].entry0;
             dev.push_back(d); which.push_back(j);
-            blocks += nb; entries += (long long)q.n_a + q.n_b;
+            blocks = plan[j].block0 + job_blocks(q.n_a, q.n_b); entries = plan[j].entry0 + q.n_a + q.n_b;
         }
         if (dev.empty()) break;
         if (int rc = grow(s, dev.size(), (size_t)entries)) return rc;
@@ -327,5 +367,51 @@ int mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_m
 }
 
 void mi_dmrecon_match_destroy(mi_dmrecon_match* m) { release(m); }
+
+/* ---- mi_dmrecon_debug.h ------------------------------------------------------------------------------------------------ */
+
+int mi_dmrecon_debug_match_get(mi_dmrecon_match* m, int32_t set, int32_t kind, int8_t* bytes_out, int32_t* off_out) {
+    if (!m) return failf(MI_DMRECON_EINVAL, "match: null handle");
+    if (kind != MATCH_SIFT && kind != MATCH_SURF) return failf(MI_DMRECON_EINVAL, "match: unknown descriptor kind %lld", kind);
+    if (set < 0 || set >= m->n_sets) return failf(MI_DMRECON_EINVAL, "match: set %lld outside [0, %lld)", set, m->n_sets);
+    std::lock_guard<std::mutex> lock(m->mu);
+    const MatchSet& s = m->sets[kind][set];
+    if (s.n == 0) return 0;
+    MATCH_HIP(hipSetDevice(m->device));
+    if (bytes_out) MATCH_HIP(hipMemcpy(bytes_out, s.d_desc, (size_t)s.n * dims_of(kind), hipMemcpyDeviceToHost));
+    if (off_out) MATCH_HIP(hipMemcpy(off_out, s.d_off, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return s.n;
+}
+
+int mi_dmrecon_debug_match_limits(long long entries, long long blocks) {
+    if (entries < 0 || blocks < 0 || blocks > MATCH_BATCH_BLOCKS)
+        return failf(MI_DMRECON_EINVAL, "match: limits (%lld, %lld) negative, or more workgroups than a launch holds (%lld)", entries, blocks,
+                     MATCH_BATCH_BLOCKS);
+    g_batch_entries.store(entries ? entries : MATCH_BATCH_ENTRIES);
+    g_batch_blocks.store(blocks ? blocks : MATCH_BATCH_BLOCKS);
+    return 0;
+}
+
+int mi_dmrecon_debug_match_plan(int32_t n_jobs, const int32_t* n_a, const int32_t* n_b, long long entries, long long blocks,
+                                int32_t* batch_out, int32_t* block0_out, int32_t* col_chunks_out, int64_t* entry0_out) {
+    try {
+        if (n_jobs < 0 || (n_jobs > 0 && (!n_a || !n_b))) return failf(MI_DMRECON_EINVAL, "match: a negative number of jobs or no sizes");
+        if (entries < 0 || blocks < 0) return failf(MI_DMRECON_EINVAL, "match: negative limits");
+        for (int32_t j = 0; j < n_jobs; ++j)
+            if (n_a[j] < 0 || n_b[j] < 0) return failf(MI_DMRECON_EINVAL, "match: job %lld has a negative size", j);
+        std::vector<MatchPlan> plan(n_jobs);
+        const int n_batches = plan_batches(n_jobs, n_a, n_b, entries ? entries : g_batch_entries.load(), blocks ? blocks : g_batch_blocks.load(),
+                                           plan.data());
+        if (n_batches < 0) return n_batches;
+        for (int32_t j = 0; j < n_jobs; ++j) {
+            if (batch_out) batch_out[j] = plan[j].batch;
+            if (block0_out) block0_out[j] = plan[j].block0;
+            if (col_chunks_out) col_chunks_out[j] = plan[j].col_chunks;
+            if (entry0_out) entry0_out[j] = plan[j].entry0;
+        }
+        return n_batches;
+    }
+    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+}
 
 }  /* extern "C" */

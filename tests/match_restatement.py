@@ -23,14 +23,19 @@ def ref_round(x):
     return np.where(x > 0, np.floor(x + F32(0.5)), np.ceil(x - F32(0.5))).astype(F32)
 
 
-def discretise(desc, kind):
+def quantise(v, scale):
+    """math::round of the float product (exhaustive_matching.cc:24, :36)."""
+    return ref_round(v * F32(scale))
+
+
+def discretise(desc, kind, quantise=quantise):
     """(n, 128) / (n, 64) float32 -> uint16 / int16, the reference's ProcessedFeatureSet storage."""
     v = np.asarray(desc, F32).reshape(-1, DIMS[kind])
     if kind == SIFT:
         v = np.where(v < 0, F32(0), np.where(v > 1, F32(1), v)).astype(F32)
-        return ref_round(v * F32(255.0)).astype(np.uint8).astype(np.uint16)
+        return quantise(v, 255.0).astype(np.uint8).astype(np.uint16)
     v = np.where(v < -1, F32(-1), np.where(v > 1, F32(1), v)).astype(F32)
-    return ref_round(v * F32(127.0)).astype(np.int8).astype(np.int16)
+    return quantise(v, 127.0).astype(np.int8).astype(np.int16)
 
 
 def inner_products(a, b):
@@ -130,6 +135,71 @@ def unit_descriptors(rng, n, kind):
     if kind == SIFT:
         v = np.abs(v)
     return (v / np.maximum(np.linalg.norm(v, axis=1, keepdims=True), 1e-12)).astype(F32)
+
+
+# ---- mutants: what a subtly wrong implementation would compute ------------------------------------------------------------
+# None of these is the reference.  tests/test_match_edges.py asserts, on the CPU and from this file alone, that each family of
+# inputs it sends to the GPU tells the restatement above from the mutant the family is aimed at: a condition on the inputs.
+
+def quantise_rint(v, scale):
+    """Mutant of quantise: round half to even (rintf)."""
+    return np.rint(v * F32(scale)).astype(F32)
+
+
+def quantise_in_double(v, scale):
+    """Mutant of quantise: product and sum in double, where neither is rounded."""
+    x = v.astype(np.float64) * scale
+    return np.where(x > 0, np.floor(x + 0.5), np.ceil(x - 0.5)).astype(F32)
+
+
+def quantise_floor_half(v, scale):
+    """Mutant of quantise: floor(x + 0.5) in float for either sign."""
+    return np.floor(v * F32(scale) + F32(0.5)).astype(F32)
+
+
+def top3_keys(ip):
+    """top2_keys with a third: (n, 3), padded with three dummies."""
+    n, m = ip.shape
+    key = np.where(ip >= 0, (ip << 32) | (np.arange(m, dtype=np.int64)[None, :] + 1), 0)
+    key = np.concatenate([key, np.zeros((n, 3), np.int64)], axis=1)
+    return -np.sort(-key, axis=1)[:, :3]
+
+
+def top2_second_is_third(ip):
+    """Mutant: the runner-up is lost and the third best reported in its place."""
+    return decode_keys(top3_keys(ip)[:, [0, 2]])
+
+
+def top2_second_is_first(ip):
+    """Mutant: the best reported twice."""
+    return decode_keys(top3_keys(ip)[:, [0, 0]])
+
+
+def top2_ties_to_smaller(ip):
+    """Mutant: the reference's loop with `>` for `>=`: among equal products the smaller index wins."""
+    n = ip.shape[0]
+    d1, d2 = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    i1, i2 = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    for j in range(ip.shape[1]):
+        v = ip[:, j]
+        first = v > d1
+        second = (v > d2) & ~first
+        d2 = np.where(first, d1, np.where(second, v, d2))
+        i2 = np.where(first, i1, np.where(second, j, i2))
+        d1 = np.where(first, v, d1)
+        i1 = np.where(first, j, i1)
+    return d1, i1, d2, i2
+
+
+def twoway_prefix(a, n_a, b, n_b, kind, lowe_ratio, distance, top2=top2_sequential):
+    """The job (a, n_a, b, n_b): the first n_a of a against the first n_b of b."""
+    return twoway(a[:n_a], b[:n_b], kind, lowe_ratio, distance, top2)
+
+
+def twoway_prefix_ignored(a, n_a, b, n_b, kind, lowe_ratio, distance, top2=top2_sequential):
+    """Mutant of twoway_prefix: the whole sets are searched, the prefixes only cut the lists of results."""
+    ab, ba = twoway(a, b, kind, lowe_ratio, distance, top2)
+    return ab[:n_a], ba[:n_b]
 
 
 # ---- the file format of tests/golden/ref_match_driver.cc ------------------------------------------------------------------
