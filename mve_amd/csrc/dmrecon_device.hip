@@ -3589,187 +3589,181 @@ using namespace MI_FWNS;
 unsigned long long* mi_debug_tbuf = nullptr;   /* the debug buffer of MI_PROBE builds (mi_dmrecon_debug_buffer) */
 #endif
 
-static void launch_optimize(hipStream_t s, int lanes_per_view, unsigned grid_blocks, const DevJob* jobs, const DevView* views,
-                        const float* lut, const DevSettings& st, const DevEntry* work, const DevHyp* hyp,
-                        DevResult* results, const unsigned* n_work_ptr, unsigned n_work, unsigned min_work,
-                        unsigned max_work, int round, DevCounters* counters, const unsigned* follow_in,
-                        const unsigned* follow_in_n, unsigned* follow_out, unsigned* follow_out_n, unsigned follow_seg,
-                        unsigned follow_seg_in, unsigned long long* follow_mask) {
-    if (grid_blocks == 0) return;
-    grid_blocks = (grid_blocks + MI_XCDS - 1) / MI_XCDS * MI_XCDS;      /* (XcdRange: every XCD the same number of workgroups) */
-    OptArgs a;
-    a.follow_seg = follow_seg; a.follow_seg_in = follow_seg_in; a.follow_mask = follow_mask;
+/* what every launch shares, as kernel arguments: no list, no hypotheses, no follow-up lists -- the launchers add theirs */
+static OptArgs base_args(const MiLaunchBase& b) {
+    OptArgs o;
+    o.jobs = b.jobs; o.views = b.views; o.lut = b.lut; o.st = b.st; o.work = nullptr; o.hyp = nullptr; o.results = nullptr;
+    o.n_work_ptr = nullptr; o.n_work = 0; o.min_work = 0; o.max_work = 0xFFFFFFFFu; o.round = 0;
+    o.counters = b.counters; o.tbuf = mi_debug_tbuf;
+    o.max_attempts = 4; o.follow_in = nullptr; o.follow_in_n = nullptr; o.follow_out = nullptr; o.follow_out_n = nullptr;
+    o.follow_seg = 0; o.follow_seg_in = 0; o.follow_mask = nullptr; o.scramble = 0;
+    return o;
+}
+template <class A> static void set_list(A& a, const MiWorkList& l) {
+    a.n_work_ptr = l.n_work_ptr; a.n_work = l.n_work; a.min_work = l.min_work; a.max_work = l.max_work; a.round = l.round;
+}
+static unsigned xcd_grid(unsigned grid_blocks) { return (grid_blocks + MI_XCDS - 1) / MI_XCDS * MI_XCDS; }   /* (XcdRange: every XCD the same number of workgroups) */
+
+static int launch_optimize(hipStream_t s, const MiLaunchBase& b, const MiOptLaunch& l) {
+    const MiFollow& f = l.follow;
+    const int K = b.st.K;
+    const bool leaves = f.out != nullptr || f.mask != nullptr;     /* a follow-up list (or the masks of one) for the rest: ONE attempt per entry */
+    switch (l.form) {       /* the combinations that have a kernel */
+    case MI_OPT_LOOP:    if (l.hyp || leaves) return 1; break;
+    /* no view selection code in it: a patch that needs one is abandoned and goes on to the follow-up list, in the end to the general kernel */
+    case MI_OPT_FAST:    if (l.hyp || !leaves || K > 8) return 1; break;
+    /* explicit hypotheses (one attempt each), or a launch that continues a follow-up list AND leaves one (process_entry_single) */
+    case MI_OPT_SINGLE:  if (!l.hyp && !(f.in && f.out)) return 1; break;
+    case MI_OPT_SEED:    if (!l.hyp || !b.st.seed_reopt) return 1; break;
+    case MI_OPT_LATENCY: if (K > 8 || f.in || leaves) return 1; break;   /* sixteen view slots: the throughput layout is all there is */
+    default: return 1;
+    }
+    if (l.grid_blocks == 0) return 0;
+    const unsigned grid_blocks = xcd_grid(l.grid_blocks);
+    OptArgs a = base_args(b);
+    set_list(a, l);
+    a.work = l.work; a.hyp = l.hyp; a.results = l.results; a.max_attempts = leaves ? 1 : 4;
+    a.follow_in = f.in; a.follow_in_n = f.in_n; a.follow_out = f.out; a.follow_out_n = f.out_n; a.follow_seg = f.seg; a.follow_seg_in = f.seg_in; a.follow_mask = f.mask;
     /* (an experiment switch: read once per process, not at every one of the hundreds of launches of a call) */
     static const unsigned scramble_env = [] { const char* e = getenv("MI_DMRECON_DEBUG_SCRAMBLE"); return e ? (unsigned)atoi(e) : 0u; }();
-    a.scramble = (follow_in == nullptr && hyp == nullptr) ? scramble_env : 0u;
-    a.jobs = jobs; a.views = views; a.lut = lut; a.st = st; a.work = work; a.hyp = hyp; a.results = results;
-    a.n_work_ptr = n_work_ptr; a.n_work = n_work; a.min_work = min_work; a.max_work = max_work;
-    a.round = round; a.counters = counters; a.tbuf = mi_debug_tbuf;
-    a.max_attempts = (follow_out || follow_mask) ? 1 : 4; a.follow_in = follow_in; a.follow_in_n = follow_in_n;
-    a.follow_out = follow_out; a.follow_out_n = follow_out_n;
-    /* lanes_per_view: 1 = throughput layout, 2 = throughput layout and the FAST kernel for a launch that CONTINUES a follow-up list
-     * (below), anything else = latency layout; st.K > 4: the eight-slot layouts */
-    const bool lat = lanes_per_view != 1 && lanes_per_view != 2, eight = st.K > 4;
-    if (st.K > 8) {
-        /* sixteen view slots: the general kernel of the throughput layout is all there is (Lay<1, 16>) -- the entries'
-         * attempts in a row, or one each where the caller keeps follow-up lists or gives explicit hypotheses */
-        if (lat) return;
-        const unsigned ncc16 = (unsigned)(Lay<1, 16>::PATCHES * st.ncc_stride * sizeof(float));
-        const bool single16 = hyp != nullptr || follow_out != nullptr;
-        if (hyp != nullptr && st.seed_reopt) hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false, true, true>), dim3(grid_blocks), dim3(WAVE), ncc16, s, a);
-        else if (single16) hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false, true>), dim3(grid_blocks), dim3(WAVE), ncc16, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false>), dim3(grid_blocks), dim3(WAVE), ncc16, s, a);
-        return;
+    a.scramble = (f.in == nullptr && l.hyp == nullptr) ? scramble_env : 0u;
+    const dim3 grid(grid_blocks), block(WAVE);
+    if (K > 8) {
+        /* sixteen view slots: the general kernel of the throughput layout is all there is (Lay<1, 16>) */
+        const unsigned ncc16 = (unsigned)(Lay<1, 16>::PATCHES * b.st.ncc_stride * sizeof(float));
+        if (l.form == MI_OPT_SEED) hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false, true, true>), grid, block, ncc16, s, a);
+        else if (l.form == MI_OPT_SINGLE) hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false, true>), grid, block, ncc16, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<1, 16>, false>), grid, block, ncc16, s, a);
+        return 0;
     }
-    /* the first launch of a bulk round (one attempt per entry, a follow-up list for the rest) runs the FAST kernel: no
-     * view selection code in it -- a patch that needs one goes to the follow-up launch, which is the general kernel */
-    /* (lanes_per_view 2: second attempts in the FAST kernel as well -- same arithmetic, a patch that needs a view selection is
-     * abandoned once more and goes on to the next list, which the general kernel takes) */
-    const bool fast = !lat && (follow_out != nullptr || follow_mask != nullptr) && (follow_in == nullptr || lanes_per_view == 2) && hyp == nullptr && st.K <= 8;
-    /* ... a launch that continues a follow-up list AND leaves one runs one attempt per entry as well, in the general kernel
-     * (process_entry_single), and so do the seeds (one hypothesis each); only a propagation launch without a follow-up list
-     * of its own runs an entry's attempts in a row */
-    const bool single = !lat && !fast && (hyp != nullptr || (follow_out != nullptr && follow_in != nullptr));
     /* the throughput kernels with a view selection in them: its NCC table in dynamic shared memory (lds_ncc) */
-    const unsigned ncc4 = (unsigned)(Lay<1, 4>::PATCHES * st.ncc_stride * sizeof(float)), ncc8 = (unsigned)(Lay<1, 8>::PATCHES * st.ncc_stride * sizeof(float));
-    if (lat) {
-        if (eight) hipLaunchKernelGGL((k_optimize<Lay<8, 8>, false>), dim3(grid_blocks), dim3(WAVE), 0, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<16, 4>, false>), dim3(grid_blocks), dim3(WAVE), 0, s, a);
-    } else if (fast) {
-        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, true>), dim3(grid_blocks), dim3(WAVE), 0, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, true>), dim3(grid_blocks), dim3(WAVE), 0, s, a);
-    } else if (single && hyp != nullptr && st.seed_reopt) {
+    const unsigned ncc4 = (unsigned)(Lay<1, 4>::PATCHES * b.st.ncc_stride * sizeof(float)), ncc8 = (unsigned)(Lay<1, 8>::PATCHES * b.st.ncc_stride * sizeof(float));
+    const bool eight = K > 4;                                            /* the eight-slot layouts */
+    switch (l.form) {
+    case MI_OPT_LATENCY:
+        if (eight) hipLaunchKernelGGL((k_optimize<Lay<8, 8>, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<16, 4>, false>), grid, block, 0, s, a);
+        break;
+    case MI_OPT_FAST:
+        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, true>), grid, block, 0, s, a);
+        break;
+    case MI_OPT_SEED:
         /* the seeds, each re-optimised once from its own result (the reference's seed semantics): a kernel of its own, so that
          * the single-attempt kernel of the propagation rounds stays what it is */
-        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false, true, true>), dim3(grid_blocks), dim3(WAVE), ncc8, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false, true, true>), dim3(grid_blocks), dim3(WAVE), ncc4, s, a);
-    } else if (single) {
-        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false, true>), dim3(grid_blocks), dim3(WAVE), ncc8, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false, true>), dim3(grid_blocks), dim3(WAVE), ncc4, s, a);
-    } else {
-        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false>), dim3(grid_blocks), dim3(WAVE), ncc8, s, a);
-        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false>), dim3(grid_blocks), dim3(WAVE), ncc4, s, a);
+        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false, true, true>), grid, block, ncc8, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false, true, true>), grid, block, ncc4, s, a);
+        break;
+    case MI_OPT_SINGLE:
+        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false, true>), grid, block, ncc8, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false, true>), grid, block, ncc4, s, a);
+        break;
+    case MI_OPT_LOOP:
+        if (eight) hipLaunchKernelGGL((k_optimize<Lay<1, 8>, false>), grid, block, ncc8, s, a);
+        else hipLaunchKernelGGL((k_optimize<Lay<1, 4>, false>), grid, block, ncc4, s, a);
+        break;
     }
+    return 0;
 }
 
-static void launch_optimize_spec(hipStream_t s, unsigned grid_blocks, const DevJob* jobs, const DevView* views, const float* lut,
-                                 const DevSettings& st, const DevEntry* work, DevSpec* spec, const unsigned* items, const unsigned* n_items,
-                                 const unsigned* n_work_ptr, unsigned n_work,
-                                 unsigned min_work, unsigned max_work, int round, DevCounters* counters) {
-    if (grid_blocks == 0) return;
-    grid_blocks = (grid_blocks + MI_XCDS - 1) / MI_XCDS * MI_XCDS;
+static void launch_optimize_spec(hipStream_t s, const MiLaunchBase& b, const MiSpecLaunch& l) {
+    if (l.grid_blocks == 0) return;
+    const unsigned grid_blocks = xcd_grid(l.grid_blocks);
     SpecArgs t;
-    t.o.jobs = jobs; t.o.views = views; t.o.lut = lut; t.o.st = st; t.o.work = work; t.o.hyp = nullptr; t.o.results = nullptr;
-    t.o.n_work_ptr = n_work_ptr; t.o.n_work = n_work; t.o.min_work = min_work; t.o.max_work = max_work; t.o.round = round;
-    t.o.counters = counters; t.o.tbuf = mi_debug_tbuf;
-    t.o.max_attempts = 1; t.o.follow_in = nullptr; t.o.follow_in_n = nullptr; t.o.follow_out = nullptr; t.o.follow_out_n = nullptr; t.o.follow_seg = 0; t.o.follow_seg_in = 0; t.o.follow_mask = nullptr; t.o.scramble = 0;
-    t.spec = spec; t.items = items; t.n_items = n_items;
-    if (st.K > 4) hipLaunchKernelGGL((k_optimize_spec<Lay<1, 8> >), dim3(grid_blocks), dim3(WAVE), (unsigned)(Lay<1, 8>::PATCHES * st.ncc_stride * sizeof(float)), s, t);
-    else hipLaunchKernelGGL((k_optimize_spec<Lay<1, 4> >), dim3(grid_blocks), dim3(WAVE), (unsigned)(Lay<1, 4>::PATCHES * st.ncc_stride * sizeof(float)), s, t);
+    t.o = base_args(b);
+    set_list(t.o, l);
+    t.o.work = l.work; t.o.max_attempts = 1;
+    t.spec = l.spec; t.items = l.items; t.n_items = l.n_items;
+    if (b.st.K > 4) hipLaunchKernelGGL((k_optimize_spec<Lay<1, 8> >), dim3(grid_blocks), dim3(WAVE), (unsigned)(Lay<1, 8>::PATCHES * b.st.ncc_stride * sizeof(float)), s, t);
+    else hipLaunchKernelGGL((k_optimize_spec<Lay<1, 4> >), dim3(grid_blocks), dim3(WAVE), (unsigned)(Lay<1, 4>::PATCHES * b.st.ncc_stride * sizeof(float)), s, t);
 }
 
-static void launch_patch_eval(hipStream_t s, const DevJob* job, const DevView* views, const float* lut,
-                          const DevSettings& st, int x, int y, float depth, float dzI, float dzJ,
-                          float* master, float* ncc, int32_t* ok, float* col, float* deriv, int32_t* level) {
+static void launch_patch_eval(hipStream_t s, const MiLaunchBase& b, const MiEvalLaunch& l) {
     EvalArgs a;
-    a.job = job; a.views = views; a.lut = lut; a.st = st; a.x = x; a.y = y; a.depth = depth; a.dzI = dzI; a.dzJ = dzJ;
-    a.master = master; a.ncc = ncc; a.ok = ok; a.col = col; a.deriv = deriv; a.level = level;
+    a.job = b.jobs; a.views = b.views; a.lut = b.lut; a.st = b.st; a.x = l.x; a.y = l.y; a.depth = l.depth; a.dzI = l.dzI; a.dzJ = l.dzJ;
+    a.master = l.master; a.ncc = l.ncc; a.ok = l.ok; a.col = l.col; a.deriv = l.deriv; a.level = l.level;
     hipLaunchKernelGGL(k_patch_eval, dim3(1), dim3(WAVE), 0, s, a);
 }
 
-static void launch_generate(hipStream_t s, const DevJob* jobs, int n_jobs, int max_tiles, DevEntry* work, DevEntry* work_lat,
-                        unsigned* round_work, unsigned* round_work_lat, unsigned* view_count, unsigned* view_mode,
-                        unsigned handover, int round, unsigned* items, unsigned* round_items, int self_round) {
+static void launch_generate(hipStream_t s, const MiLaunchBase& b, const MiGenLaunch& l) {
     SweepArgs a;
-    a.self_round = self_round;
-    a.jobs = jobs; a.work = work; a.work_lat = work_lat; a.round_work = round_work; a.round_work_lat = round_work_lat;
-    a.view_count = view_count; a.view_mode = view_mode; a.handover = handover; a.n_jobs = n_jobs; a.round = round;
-    a.items = items; a.round_items = round_items;
-    hipLaunchKernelGGL(k_generate, dim3(max_tiles, n_jobs), dim3(256), 0, s, a);
+    a.self_round = l.self_round;
+    a.jobs = b.jobs; a.work = l.work; a.work_lat = l.work_lat; a.round_work = l.round_work; a.round_work_lat = l.round_work_lat;
+    a.view_count = l.view_count; a.view_mode = l.view_mode; a.handover = l.handover; a.n_jobs = l.n_jobs; a.round = l.round;
+    a.items = l.items; a.round_items = l.round_items;
+    hipLaunchKernelGGL(k_generate, dim3(l.max_tiles, l.n_jobs), dim3(256), 0, s, a);
 }
 
 #if MI_FW == 5
-void mi_launch_apply(hipStream_t s, unsigned grid_blocks, const DevJob* jobs, const DevEntry* work, const DevResult* results,
-                     const unsigned* n_work_ptr, unsigned n_work, unsigned min_work, unsigned max_work, int round, DevCounters* counters) {
-    if (grid_blocks == 0) return;
+/* k_apply / k_apply_spec / k_apply_seeds: the work list of a launch; the launchers add what they apply */
+static ApplyArgs apply_args(const MiLaunchBase& b, const MiWorkList& l, const DevEntry* work) {
     ApplyArgs a;
-    a.jobs = jobs; a.work = work; a.results = results; a.spec = nullptr; a.items = nullptr; a.n_items = nullptr; a.n_work_ptr = n_work_ptr; a.n_work = n_work;
-    a.min_work = min_work; a.max_work = max_work; a.round = round;
-    a.counters = counters; a.seed_keys = nullptr; a.key_off = nullptr; a.phase = 0; a.seed_reopt = 0; a.seed_count = nullptr;
+    set_list(a, l);
+    a.jobs = b.jobs; a.work = work; a.results = nullptr; a.spec = nullptr; a.items = nullptr; a.n_items = nullptr;
+    a.counters = b.counters; a.seed_keys = nullptr; a.key_off = nullptr; a.phase = 0; a.seed_reopt = 0; a.seed_count = nullptr;
+    return a;
+}
+void mi_launch_apply(hipStream_t s, const MiLaunchBase& b, const MiOptLaunch& l, unsigned grid_blocks) {
+    if (grid_blocks == 0) return;
+    ApplyArgs a = apply_args(b, l, l.work);
+    a.results = l.results;
     hipLaunchKernelGGL(k_apply, dim3(grid_blocks), dim3(256), 0, s, a);
 }
-void mi_launch_apply_spec(hipStream_t s, unsigned grid_blocks, const DevJob* jobs, const DevEntry* work, const DevSpec* spec,
-                          const unsigned* items, const unsigned* n_items,
-                          const unsigned* n_work_ptr, unsigned n_work, unsigned min_work, unsigned max_work, int round, DevCounters* counters) {
-    if (grid_blocks == 0) return;
-    ApplyArgs a;
-    a.jobs = jobs; a.work = work; a.results = nullptr; a.spec = spec; a.items = items; a.n_items = n_items; a.n_work_ptr = n_work_ptr; a.n_work = n_work;
-    a.min_work = min_work; a.max_work = max_work; a.round = round;
-    a.counters = counters; a.seed_keys = nullptr; a.key_off = nullptr; a.phase = 0; a.seed_reopt = 0; a.seed_count = nullptr;
-    hipLaunchKernelGGL(k_apply_spec, dim3(grid_blocks), dim3(256), 0, s, a);
+void mi_launch_apply_spec(hipStream_t s, const MiLaunchBase& b, const MiSpecLaunch& l) {
+    if (l.grid_blocks == 0) return;
+    ApplyArgs a = apply_args(b, l, l.work);
+    a.spec = l.spec; a.items = l.items; a.n_items = l.n_items;
+    hipLaunchKernelGGL(k_apply_spec, dim3(l.grid_blocks), dim3(256), 0, s, a);
 }
 
 #endif
 
-static void launch_tail(hipStream_t s, unsigned grid_blocks, const DevJob* jobs, const DevView* views, const float* lut,
-                    const DevSettings& st, const DevEntry* prev_work, const DevResult* prev_results, DevEntry* work,
-                    DevResult* results, unsigned* round_work, int round, DevCounters* counters, bool speculative) {
+static void launch_tail(hipStream_t s, const MiLaunchBase& b, const MiTailLaunch& l) {
     TailArgs t;
-    t.o.jobs = jobs; t.o.views = views; t.o.lut = lut; t.o.st = st; t.o.work = work; t.o.hyp = nullptr; t.o.results = results;
-    t.o.n_work_ptr = nullptr; t.o.n_work = 0; t.o.min_work = 0; t.o.max_work = 0xFFFFFFFFu; t.o.round = round;
-    t.o.counters = counters; t.o.tbuf = mi_debug_tbuf;
-    t.o.max_attempts = 4; t.o.follow_in = nullptr; t.o.follow_in_n = nullptr; t.o.follow_out = nullptr; t.o.follow_out_n = nullptr; t.o.follow_seg = 0; t.o.follow_seg_in = 0; t.o.follow_mask = nullptr; t.o.scramble = 0;
-    t.prev_work = prev_work; t.prev_results = prev_results; t.round_work = round_work;
-    if (st.K > 4) {
-        if (speculative) hipLaunchKernelGGL((k_tail<true, 8>), dim3(grid_blocks), dim3(MI_TAIL_WAVES * WAVE), 0, s, t);
-        else hipLaunchKernelGGL((k_tail<false, 8>), dim3(grid_blocks), dim3(WAVE), 0, s, t);
+    t.o = base_args(b);
+    t.o.work = l.work; t.o.results = l.results; t.o.round = l.round;
+    t.prev_work = l.prev_work; t.prev_results = l.prev_results; t.round_work = l.round_work;
+    if (b.st.K > 4) {
+        if (l.speculative) hipLaunchKernelGGL((k_tail<true, 8>), dim3(l.grid_blocks), dim3(MI_TAIL_WAVES * WAVE), 0, s, t);
+        else hipLaunchKernelGGL((k_tail<false, 8>), dim3(l.grid_blocks), dim3(WAVE), 0, s, t);
     } else {
-        if (speculative) hipLaunchKernelGGL((k_tail<true, 4>), dim3(grid_blocks), dim3(MI_TAIL_WAVES * WAVE), 0, s, t);
-        else hipLaunchKernelGGL((k_tail<false, 4>), dim3(grid_blocks), dim3(WAVE), 0, s, t);
+        if (l.speculative) hipLaunchKernelGGL((k_tail<true, 4>), dim3(l.grid_blocks), dim3(MI_TAIL_WAVES * WAVE), 0, s, t);
+        else hipLaunchKernelGGL((k_tail<false, 4>), dim3(l.grid_blocks), dim3(WAVE), 0, s, t);
     }
 }
 
-static void launch_front(hipStream_t s, int n_jobs, const DevJob* jobs, const DevView* views, const float* lut, const DevSettings& st,
-                         const DevEntry* list, const DevResult* list_results, const unsigned* list_n,
-                         DevEntry* work0, DevResult* results0, DevEntry* work1, DevResult* results1,
-                         const unsigned* job_off, unsigned* job_count, unsigned* job_stats, int first_round, int max_rounds,
-                         DevCounters* counters, int team, unsigned long long* mail, unsigned* team_flags,
-                         const unsigned long long* job_start, unsigned long long* job_resume, unsigned* team_filled, unsigned spin_ticks,
-                         int fault, int n_xcd, unsigned* host_done, const unsigned* block_map, unsigned grid_blocks, const unsigned* job_order) {
+static void launch_front(hipStream_t s, const MiLaunchBase& b, const MiFrontLaunch& l) {
     static_assert(MI_FRONT_MAIL_WORDS == 2 * MI_FRONT_QCAP * 4 * MI_FRONT_GRAN, "mailbox size");
-    if (n_jobs <= 0) return;
-    if (!job_start) {
+    if (l.n_jobs <= 0) return;
+    if (!l.job_start) {
         FrontSplitArgs sp;
-        sp.work = list; sp.results = list_results; sp.n_ptr = list_n; sp.owork = work0; sp.oresults = results0;
-        sp.job_off = job_off; sp.job_count = job_count;
+        sp.work = l.list; sp.results = l.list_results; sp.n_ptr = l.list_n; sp.owork = l.work[0]; sp.oresults = l.results[0];
+        sp.job_off = l.job_off; sp.job_count = l.job_count;
         hipLaunchKernelGGL(k_front_split, dim3(16), dim3(256), 0, s, sp);
     }
     FrontArgs t;
-    t.o.jobs = jobs; t.o.views = views; t.o.lut = lut; t.o.st = st; t.o.work = nullptr; t.o.hyp = nullptr; t.o.results = nullptr;
-    t.o.n_work_ptr = nullptr; t.o.n_work = 0; t.o.min_work = 0; t.o.max_work = 0xFFFFFFFFu; t.o.round = first_round;
-    t.o.counters = counters; t.o.tbuf = mi_debug_tbuf;
-    t.o.max_attempts = 4; t.o.follow_in = nullptr; t.o.follow_in_n = nullptr; t.o.follow_out = nullptr; t.o.follow_out_n = nullptr; t.o.follow_seg = 0; t.o.follow_seg_in = 0; t.o.follow_mask = nullptr; t.o.scramble = 0;
-    t.work[0] = work0; t.work[1] = work1; t.results[0] = results0; t.results[1] = results1;
-    t.job_off = job_off; t.job_count = job_count; t.job_start = job_start; t.job_resume = job_resume;
-    t.job_stats = job_stats; t.max_rounds = max_rounds;
-    t.team = 1; t.mail = nullptr; t.team_flags = nullptr; t.team_filled = team_filled; t.spin_ticks = spin_ticks;
-    t.fault_member = fault < 0 ? -1 : (fault & 0xFF); t.fault_round = fault < 0 ? 0 : ((fault >> 8) & 0xFFFF);
-    t.force_write_through = fault >= 0 && ((fault >> 24) & 1) != 0;
-    if (fault >= 0 && (fault & 0xFF) == 0xFF) t.fault_member = -1;          /* (write-through forced, nobody vanishes) */
-    t.n_jobs = n_jobs; t.n_xcd = n_xcd < 1 ? 1 : n_xcd;
-    t.l2_exchange = (fault >= 0 && ((fault >> 25) & 1)) ? 0 : 1;
-    t.host_done = host_done;
-    t.block_map = nullptr; t.job_order = job_order;
-    if (team > 1 && mail && team_flags && team_filled && block_map && grid_blocks > 0) {
-        t.team = team > MI_FRONT_TEAM_MAX ? MI_FRONT_TEAM_MAX : team; t.mail = mail; t.team_flags = team_flags;
-        t.block_map = block_map;
-        const unsigned grid = grid_blocks;
-        if (st.K > 4) hipLaunchKernelGGL((k_front<8, true>), dim3(grid), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
-        else hipLaunchKernelGGL((k_front<4, true>), dim3(grid), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
-        hipLaunchKernelGGL(k_front_commit, dim3((unsigned)(n_jobs + 255) / 256), dim3(256), 0, s, jobs, team_filled, counters, n_jobs);
+    t.o = base_args(b);
+    t.o.round = l.first_round;
+    t.work[0] = l.work[0]; t.work[1] = l.work[1]; t.results[0] = l.results[0]; t.results[1] = l.results[1];
+    t.job_off = l.job_off; t.job_count = l.job_count; t.job_start = l.job_start; t.job_resume = l.job_resume;
+    t.job_stats = l.job_stats; t.max_rounds = l.max_rounds;
+    t.team = 1; t.mail = nullptr; t.team_flags = nullptr; t.team_filled = l.team_filled; t.spin_ticks = l.spin_ticks;
+    t.fault_member = l.debug.vanish_member; t.fault_round = l.debug.vanish_round;
+    t.force_write_through = l.debug.write_through;
+    t.n_jobs = l.n_jobs; t.n_xcd = l.n_xcd < 1 ? 1 : l.n_xcd;
+    t.l2_exchange = l.debug.exchange_through_memory ? 0 : 1;
+    t.host_done = l.host_done;
+    t.block_map = nullptr; t.job_order = l.job_order;
+    const MiFrontTeam& tm = l.team;
+    if (tm.size > 1 && tm.mail && tm.flags && l.team_filled && tm.block_map && tm.grid_blocks > 0) {
+        t.team = tm.size > MI_FRONT_TEAM_MAX ? MI_FRONT_TEAM_MAX : tm.size; t.mail = tm.mail; t.team_flags = tm.flags;
+        t.block_map = tm.block_map;
+        if (b.st.K > 4) hipLaunchKernelGGL((k_front<8, true>), dim3(tm.grid_blocks), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
+        else hipLaunchKernelGGL((k_front<4, true>), dim3(tm.grid_blocks), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
+        hipLaunchKernelGGL(k_front_commit, dim3((unsigned)(l.n_jobs + 255) / 256), dim3(256), 0, s, b.jobs, l.team_filled, b.counters, l.n_jobs);
     }
-    else if (st.K > 4) hipLaunchKernelGGL((k_front<8, false>), dim3((unsigned)n_jobs), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
-    else hipLaunchKernelGGL((k_front<4, false>), dim3((unsigned)n_jobs), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
+    else if (b.st.K > 4) hipLaunchKernelGGL((k_front<8, false>), dim3((unsigned)l.n_jobs), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
+    else hipLaunchKernelGGL((k_front<4, false>), dim3((unsigned)l.n_jobs), dim3(MI_FRONT_WAVES * WAVE), 0, s, t);
 }
 
 #if MI_FW == 5
@@ -3788,30 +3782,25 @@ void mi_launch_flatten(hipStream_t s, float* maps, uint32_t* imaps, size_t total
 }
 
 void mi_launch_emit_changed(hipStream_t s, const float* maps, const uint32_t* imaps, size_t total_px, size_t first, size_t count,
-                            int r0, unsigned view, unsigned stride, unsigned* d_count, unsigned cap, uint32_t* out) {
+                            const MiEmitLaunch& l) {
     if (total_px == 0 || count == 0) return;
     EmitArgs a;
     a.depth = maps + first; a.conf = maps + total_px + first; a.dz = maps + 2 * total_px + 2 * first; a.normal = maps + 4 * total_px + 3 * first;
     const float* m1 = maps + 7 * total_px;
     a.depth1 = m1 + first; a.conf1 = m1 + total_px + first; a.dz1 = m1 + 2 * total_px + 2 * first; a.normal1 = m1 + 4 * total_px + 3 * first;
     a.upd = (const int32_t*)(imaps + total_px + first); a.upd1 = (const int32_t*)(imaps + 3 * total_px + first);
-    a.n = (unsigned)count; a.r0 = r0; a.view = view; a.stride = stride; a.count = d_count; a.cap = cap; a.out = out;
+    a.n = (unsigned)count; a.r0 = l.r0; a.view = l.view; a.stride = l.stride; a.count = l.d_count; a.cap = l.cap; a.out = l.out;
     hipLaunchKernelGGL(k_emit_changed, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, a);
 }
 
-void mi_launch_apply_seeds(hipStream_t s, const DevJob* jobs, const DevEntry* work, const DevResult* results,
-                           unsigned n_work, DevCounters* counters, unsigned long long* seed_keys,
+void mi_launch_apply_seeds(hipStream_t s, const MiLaunchBase& b, const MiOptLaunch& l, unsigned long long* seed_keys,
                            const unsigned* key_off, int seed_reopt, unsigned* seed_count) {
-    if (n_work == 0) return;
-    ApplyArgs a;
-    a.seed_reopt = seed_reopt; a.seed_count = seed_count;
-    a.jobs = jobs; a.work = work; a.results = results; a.spec = nullptr; a.items = nullptr; a.n_items = nullptr; a.n_work_ptr = nullptr; a.n_work = n_work; a.round = 0;
-    a.min_work = 0; a.max_work = 0xFFFFFFFFu;
-    a.counters = counters; a.seed_keys = seed_keys; a.key_off = key_off;
-    a.phase = 0;
-    hipLaunchKernelGGL(k_apply_seeds, dim3((n_work + 255) / 256), dim3(256), 0, s, a);
+    if (l.n_work == 0) return;
+    ApplyArgs a = apply_args(b, l, l.work);
+    a.results = l.results; a.seed_reopt = seed_reopt; a.seed_count = seed_count; a.seed_keys = seed_keys; a.key_off = key_off;
+    hipLaunchKernelGGL(k_apply_seeds, dim3((l.n_work + 255) / 256), dim3(256), 0, s, a);
     a.phase = 1;
-    hipLaunchKernelGGL(k_apply_seeds, dim3((n_work + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_apply_seeds, dim3((l.n_work + 255) / 256), dim3(256), 0, s, a);
 }
 
 void mi_launch_round_report(hipStream_t s, const unsigned* a, int n_a, const unsigned* b, int n_b, const DevCounters* counters,
@@ -3819,10 +3808,10 @@ void mi_launch_round_report(hipStream_t s, const unsigned* a, int n_a, const uns
     hipLaunchKernelGGL(k_round_report, dim3(1), dim3(256), 0, s, a, n_a, b, n_b, counters, jobs, n_jobs, out_rw,
                        reinterpret_cast<unsigned*>(out_hc), static_cast<unsigned*>(out_dyn), view_count);
 }
-void mi_launch_follow_compact(hipStream_t s, const unsigned long long* mask, const unsigned* n_work_ptr, unsigned min_work, unsigned max_work,
-                              unsigned ppw, unsigned lpp, unsigned* blk_sum, unsigned* out, unsigned* out_n) {
+void mi_launch_follow_compact(hipStream_t s, const MiWorkList& l, const unsigned long long* mask, unsigned ppw, unsigned lpp,
+                              unsigned* blk_sum, unsigned* out, unsigned* out_n) {
     FollowArgs a;
-    a.mask = mask; a.n_work_ptr = n_work_ptr; a.min_work = min_work; a.max_work = max_work; a.ppw = ppw; a.lpp = lpp;
+    a.mask = mask; a.n_work_ptr = l.n_work_ptr; a.min_work = l.min_work; a.max_work = l.max_work; a.ppw = ppw; a.lpp = lpp;
     a.blk_sum = blk_sum; a.out = out; a.out_n = out_n;
     hipLaunchKernelGGL(k_follow_count, dim3(MI_FOLLOW_BLOCKS), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_follow_scatter, dim3(MI_FOLLOW_BLOCKS), dim3(256), 0, s, a);
@@ -3844,9 +3833,8 @@ void mi_launch_pack_rgba(hipStream_t s, const uint8_t* src, uint32_t* dst, int n
 void mi_launch_unpack_rgb(hipStream_t s, const uint32_t* src, uint8_t* dst, int n) {
     hipLaunchKernelGGL(k_unpack_rgb, dim3((n + 255) / 256), dim3(256), 0, s, src, dst, n);
 }
-void mi_launch_pyramid(hipStream_t s, const uint32_t* src, uint32_t* dst, int iw, int ih, int ow, int oh,
-                       float w1, float w2, float w3) {
-    hipLaunchKernelGGL(k_pyramid, dim3((ow + 63) / 64, (oh + 3) / 4), dim3(256), 0, s, src, dst, iw, ih, ow, oh, w1, w2, w3);
+void mi_launch_pyramid(hipStream_t s, const uint32_t* src, uint32_t* dst, int iw, int ih, int ow, int oh, const float w[3]) {
+    hipLaunchKernelGGL(k_pyramid, dim3((ow + 63) / 64, (oh + 3) / 4), dim3(256), 0, s, src, dst, iw, ih, ow, oh, w[0], w[1], w[2]);
 }
 #endif
 

@@ -236,6 +236,8 @@ std::atomic<int> g_inject_footprint(-1);     /* test hook, see fill_job */
 #define MI_TEAM_WAIT_US 20000u     /* a front team member waits this long for the others before the team gives up */
 #define MI_FRONT_MIN_CAP 256       /* hand-over to k_front: entries per view, at least */
 #define MI_FRONT_PER_TEAM_WG 64    /* ... and per workgroup of a view's team */
+/* a numeric run-time switch, or `dflt` if it is not set (the readers clamp, and decide how often they look) */
+static long env_or(const char* name, long dflt) { const char* e = std::getenv(name); return e ? std::atol(e) : dflt; }
 struct ActiveCall {
     int dev;
     explicit ActiveCall(int d) : dev(d >= 0 && d < MI_MAX_DEVICES ? d : -1) { if (dev >= 0) g_active_calls[dev].fetch_add(1); }
@@ -1592,10 +1594,10 @@ static int set_view_impl(mi_dmrecon_ctx* c, int32_t view_id, const mi_dmrecon_ca
     }
     HIP_TRY(hipMemcpyAsync(stage.p, pixels, nbytes, hipMemcpyHostToDevice, c->stream));
     mi_launch_pack_rgba(c->stream, stage.p, v.d_img, width * height, channels);
-    const float w1 = std::exp(-0.5f / (2.0f * 1.f)), w2 = std::exp(-2.5f / (2.0f * 1.f)), w3 = std::exp(-4.5f / (2.0f * 1.f));
+    const float w[3] = {std::exp(-0.5f / (2.0f * 1.f)), std::exp(-2.5f / (2.0f * 1.f)), std::exp(-4.5f / (2.0f * 1.f))};
     for (size_t l = 1; l < v.levels.size(); ++l) {
         HostLevel const& a = v.levels[l - 1]; HostLevel const& b = v.levels[l];
-        mi_launch_pyramid(c->stream, v.d_img + a.tex_off, v.d_img + b.tex_off, a.w, a.h, b.w, b.h, w1, w2, w3);
+        mi_launch_pyramid(c->stream, v.d_img + a.tex_off, v.d_img + b.tex_off, a.w, a.h, b.w, b.h, w);
     }
     for (size_t l = 0; l < v.levels.size(); ++l) {
         HostLevel const& a = v.levels[l];
@@ -1737,7 +1739,8 @@ struct BatchRun {
     /* the call */
     mi_dmrecon_ctx* c; const mi_dmrecon_settings* st; int n_refs; const int32_t* ref_views;
     mi_dmrecon_maps* maps; mi_dmrecon_progress* progress; int32_t* status_out; mi_dmrecon_stats* stats;
-    const MiDeviceApi* D; DevSettings ds; hipStream_t S;
+    const MiDeviceApi* D; hipStream_t S;
+    MiLaunchBase base;                         /* what every launch of the batch shares (the settings from the start, the rest from upload()) */
     bool trace; double t_begin, t_mark;
     /* the plan: one job per reference view that got through the host planning */
     std::vector<int> view_rc, job_of, ref_of_job;
@@ -2017,6 +2020,7 @@ int BatchRun::upload() {
         c->bs.h_dyn_cap = want;
     }
     n_alive = nj;
+    base.jobs = c->bs.d_jobs.p; base.views = c->sc->d_views.p; base.lut = c->sc->d_lut; base.counters = c->d_counters;
     mark("setup + uploads (async)");
     return 0;
 }
@@ -2038,18 +2042,18 @@ int BatchRun::seed_round() {
      * written in round 1, the others as round 0's, k_apply_seeds counts the pixels per view as the size of "round 1", and the
      * propagation starts with round 2: the maps of the two-round form (seed_mode 1: round 1 re-optimises the pixels the seeds
      * wrote), bit for bit, without a round of its own. */
-    DevSettings sds = ds;
-    sds.seed_reopt = seed_mode == 2 ? 1 : 0;
-    D->optimize(S, 1, ((unsigned)n_seeds_total + ppw - 1) / ppw, c->bs.d_jobs.p, c->sc->d_views.p,
-                c->sc->d_lut, sds, c->bs.d_work.p, c->bs.d_hyp.p, c->bs.d_results.p, nullptr, (unsigned)n_seeds_total, 0u, 0xFFFFFFFFu, 0,
-                c->d_counters, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr);
+    MiLaunchBase sb = base;
+    sb.st.seed_reopt = seed_mode == 2 ? 1 : 0;
+    MiOptLaunch seeds;
+    seeds.form = sb.st.seed_reopt ? MI_OPT_SEED : MI_OPT_SINGLE; seeds.grid_blocks = ((unsigned)n_seeds_total + ppw - 1) / ppw;
+    seeds.work = c->bs.d_work.p; seeds.hyp = c->bs.d_hyp.p; seeds.results = c->bs.d_results.p; seeds.n_work = (unsigned)n_seeds_total;
+    if (D->optimize(S, sb, seeds)) return fail(MI_DMRECON_EDEVICE, "internal: no kernel for the seed launch");
     ev.end(S);
     ++n_launch;
     ev.begin(S, EventLog::SWEEP, 0);
-    mi_launch_apply_seeds(S, c->bs.d_jobs.p, c->bs.d_work.p, c->bs.d_results.p, (unsigned)n_seeds_total, c->d_counters, c->bs.d_keys.p, c->bs.d_keyoff.p,
-                          sds.seed_reopt, c->bs.d_view.p + (size_t)nj);
+    mi_launch_apply_seeds(S, sb, seeds, c->bs.d_keys.p, c->bs.d_keyoff.p, sb.st.seed_reopt, c->bs.d_view.p + (size_t)nj);
     ev.end(S);
-    if (sds.seed_reopt) round = 2;
+    if (sb.st.seed_reopt) round = 2;
     return 0;
 }
 
@@ -2086,7 +2090,7 @@ int BatchRun::bulk_rounds(bool& to_tail) {
     /* MI_DMRECON_ONE_LAUNCH=<entries> (read per call): rounds below this many entries in the throughput layout run as one
      * launch of the general kernel (below) */
     const bool wide = st->nrReconNeighbors > 8;      /* sixteen view slots: the general kernel, one launch per round, nothing speculative */
-    const unsigned ONE_LAUNCH_MAX = wide ? 0xFFFFFFFFu : [] { const char* e = std::getenv("MI_DMRECON_ONE_LAUNCH"); return e ? (unsigned)std::max(0L, std::atol(e)) : MI_ONE_LAUNCH_MAX; }();
+    const unsigned ONE_LAUNCH_MAX = wide ? 0xFFFFFFFFu : (unsigned)std::max(0L, env_or("MI_DMRECON_ONE_LAUNCH", MI_ONE_LAUNCH_MAX));
     const int max_rounds = MI_MAX_ROUNDS - 2 * (int)MI_TAIL_CHUNK - 2;
     unsigned* d_vcount = c->bs.d_view.p; unsigned* d_vmode = d_vcount + 3 * (size_t)nj;
     const unsigned ppw = patches_per_wave(st);
@@ -2095,13 +2099,13 @@ int BatchRun::bulk_rounds(bool& to_tail) {
      * every (entry, rank) pair gets a quad of its own (k_optimize_spec / k_apply_spec: same maps, same counters).  The
      * records are sized for twice the threshold; a round that turns out larger than that runs the plain launches, which
      * are enqueued next to the speculative ones and look at the size on the device. */
-    const unsigned SPEC_MAX = wide ? 0u : [] { const char* e = std::getenv("MI_DMRECON_SPEC_ROUNDS"); return e ? (unsigned)std::max(0L, std::atol(e)) : MI_SPEC_ROUNDS; }();
+    const unsigned SPEC_MAX = wide ? 0u : (unsigned)std::max(0L, env_or("MI_DMRECON_SPEC_ROUNDS", MI_SPEC_ROUNDS));
     const unsigned spec_cap = 2u * SPEC_MAX;
     /* MI_DMRECON_SINGLE_FOLLOW=<n> (read per call): 0 = the follow-up list of a large round in ONE launch, all remaining attempts
      * of an entry in a row (round 4's form); n = 1 .. 3: n single-attempt follow-up launches, then one for the rest; 4: every
      * further attempt a launch of its own.  Same maps and counters. */
-    const int SINGLE_FOLLOW = [] { const char* e = std::getenv("MI_DMRECON_SINGLE_FOLLOW"); return e ? std::atoi(e) : MI_SINGLE_FOLLOW; }();
-    const int FAST_FOLLOW = wide ? 0 : [] { const char* e = std::getenv("MI_DMRECON_FAST_FOLLOW"); return e ? std::max(0, std::min(3, std::atoi(e))) : MI_FAST_FOLLOW; }();
+    const int SINGLE_FOLLOW = (int)env_or("MI_DMRECON_SINGLE_FOLLOW", MI_SINGLE_FOLLOW);
+    const int FAST_FOLLOW = wide ? 0 : (int)std::max(0L, std::min(3L, env_or("MI_DMRECON_FAST_FOLLOW", MI_FAST_FOLLOW)));
     if (SPEC_MAX > 0 && c->bs.d_spec.reserve(4 * (size_t)spec_cap)) return fail(MI_DMRECON_EDEVICE, "hipMalloc(speculative records) failed");
     /* The rounds are enqueued WITHOUT waiting for their list sizes: every kernel of a round reads its size on the device
      * (k_generate also decides there which layout a view's entries go to), the grids come from the sizes of the last round
@@ -2125,13 +2129,16 @@ int BatchRun::bulk_rounds(bool& to_tail) {
          * ones (below) only above it */
         const bool spec = SPEC_MAX > 0 && known_thr < SPEC_MAX;
         const bool self = SEED_REOPT && r == 1;
-        DevSettings ds = this->ds;                                   /* (shadows the member for this round's launches) */
-        ds.self_round = self ? 1 : 0;
-        ev.begin(S, EventLog::SWEEP, 0);
-        D->generate(S, c->bs.d_jobs.p, nj, max_tiles, c->bs.d_work.p, c->bs.d_work2.p, c->bs.d_round_work_t.p, c->bs.d_round_work.p,
-                    d_vcount, d_vmode, handover, r, spec ? c->bs.d_follow.p : nullptr, c->bs.d_round_items.p, self ? 1 : 0);
-        ev.end(S);
+        MiLaunchBase rb = base;                                      /* (this round's launches: the batch's, with the round's settings) */
+        rb.st.self_round = self ? 1 : 0;
         const unsigned* n_thr_p = c->bs.d_round_work_t.p + r; const unsigned* n_lat_p = c->bs.d_round_work.p + r;
+        ev.begin(S, EventLog::SWEEP, 0);
+        MiGenLaunch gen;
+        gen.n_jobs = nj; gen.max_tiles = max_tiles; gen.handover = handover; gen.round = r; gen.self_round = rb.st.self_round;
+        gen.work = c->bs.d_work.p; gen.round_work = c->bs.d_round_work_t.p; gen.work_lat = c->bs.d_work2.p; gen.round_work_lat = c->bs.d_round_work.p;
+        gen.view_count = d_vcount; gen.view_mode = d_vmode; gen.items = spec ? c->bs.d_follow.p : nullptr; gen.round_items = c->bs.d_round_items.p;
+        D->generate(S, rb, gen);
+        ev.end(S);
         const unsigned est = std::max(2u * known_thr, 65536u);
         /* The grid of a large round is sized for MI_BULK_UNITS units of ppw patches per wavefront (k_optimize strides over the list):
          * a wavefront's prologue (table load, barrier) and its counter flush are paid once per that many units -- 1 / 2 / 4 units:
@@ -2152,11 +2159,22 @@ int BatchRun::bulk_rounds(bool& to_tail) {
          * round before), and the host's figure is two rounds old when it enqueues: below a sixteenth of the records' capacity
          * the plain launches cannot be needed */
         const bool need_plain = !spec || 16ull * (unsigned long long)known_thr >= (unsigned long long)spec_cap;
+        /* the round's two lists (their sizes stay on the device).  The throughput list as the plain launches see it, from plain_min
+         * entries on; below spec_cap as the speculative ones do */
+        MiOptLaunch thr, lat;
+        thr.n_work_ptr = n_thr_p; thr.round = r; thr.min_work = plain_min; thr.work = c->bs.d_work.p; thr.results = c->bs.d_results.p;
+        lat.n_work_ptr = n_lat_p; lat.round = r; lat.work = c->bs.d_work2.p; lat.results = c->bs.d_results2.p;
+        /* (items: ~1.3 per entry; the list of them is the follow-up buffer, which a speculative round does not use) */
+        MiSpecLaunch sp;
+        sp.n_work_ptr = n_thr_p; sp.round = r; sp.max_work = spec_cap; sp.work = thr.work; sp.spec = c->bs.d_spec.p; sp.items = c->bs.d_follow.p; sp.n_items = c->bs.d_round_items.p + r;
+        /* a launch over one of the lists (what else it needs is in l); a form that has no kernel for it: an error of this function's */
+        auto run = [&](MiOptLaunch l, MiOptForm form, unsigned grid) -> int {
+            l.form = form; l.grid_blocks = grid;
+            return D->optimize(S, rb, l) ? fail(MI_DMRECON_EDEVICE, "internal: round %d asks for a launch (form %d) that has no kernel", r, (int)form) : 0;
+        };
         if (spec) {
-            /* (items: ~1.3 per entry; the list of them is the follow-up buffer, which a speculative round does not use) */
-            const unsigned quads = std::min(std::max(3u * known_thr, 16384u), 4u * spec_cap);
-            D->optimize_spec(S, (quads + ppw - 1) / ppw, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, c->bs.d_spec.p,
-                             c->bs.d_follow.p, c->bs.d_round_items.p + r, n_thr_p, 0u, 0u, spec_cap, r, c->d_counters);
+            sp.grid_blocks = (std::min(std::max(3u * known_thr, 16384u), 4u * spec_cap) + ppw - 1) / ppw;
+            D->optimize_spec(S, rb, sp);
         }
         /* Rounds below MI_ONE_LAUNCH_MAX entries run as ONE launch of the general kernel, all attempts of an entry in a
          * row: such a launch fits the GPU at once, so either launch of the two-launch form lasts one wavefront-life
@@ -2165,9 +2183,7 @@ int BatchRun::bulk_rounds(bool& to_tail) {
          * 546 / 540).  Same arithmetic either way (tests: the maps do not depend on the form); chosen from the last
          * size the host has seen. */
         if (!need_plain) { }
-        else if (known_thr < ONE_LAUNCH_MAX)
-            D->optimize(S, 1, spec ? std::max(1u, waves / 2) : waves, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr, c->bs.d_results.p, n_thr_p,
-                        0u, plain_min, 0xFFFFFFFFu, r, c->d_counters, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr);
+        else if (known_thr < ONE_LAUNCH_MAX) { if (int rc = run(thr, MI_OPT_LOOP, spec ? std::max(1u, waves / 2) : waves)) return rc; }
         else {
             /* one optimisation attempt per entry and launch; the entries whose pixel has further candidate hypotheses
              * (about one in five) continue in a follow-up launch over a compacted list (its size stays on the device),
@@ -2177,7 +2193,7 @@ int BatchRun::bulk_rounds(bool& to_tail) {
              * MI_FOLLOW_SEGS segments -- one per XCD, with a counter of its own (OptArgs::follow_seg) -- of an eighth of the
              * batch's pixels (+ slack: an XCD's eighth of a list is rounded up to whole wavefronts) */
             /* (MI_DMRECON_FOLLOW_SEGMENTS=0, read per call: one list for all XCDs, as until round 6 -- the A/B switch; same maps) */
-            const bool segs = [] { const char* e = std::getenv("MI_DMRECON_FOLLOW_SEGMENTS"); return !e || std::atoi(e) != 0; }();
+            const bool segs = env_or("MI_DMRECON_FOLLOW_SEGMENTS", 1) != 0;
             const unsigned fseg_full = (unsigned)((total_px + MI_FOLLOW_SEGS - 1) / MI_FOLLOW_SEGS) + 64u;
             const unsigned fseg = segs ? fseg_full : 0u;
             const size_t fstride = (size_t)fseg_full * MI_FOLLOW_SEGS;
@@ -2187,13 +2203,24 @@ int BatchRun::bulk_rounds(bool& to_tail) {
              * list from the masks -- a wavefront of it then holds entries of one view and a few image rows instead of 16 strangers,
              * whose footprint gathers share no cache line (1.76 x slower per sampling pass: OptArgs::follow_mask). */
             static const bool scrambled = std::getenv("MI_DMRECON_DEBUG_SCRAMBLE") != nullptr;   /* (read once per process, as the launcher does) */
-            const bool ordered = SINGLE_FOLLOW && !scrambled
-                && [] { const char* e = std::getenv("MI_DMRECON_FOLLOW_ORDERED"); return !e || std::atoi(e) != 0; }();
+            const bool ordered = SINGLE_FOLLOW && !scrambled && env_or("MI_DMRECON_FOLLOW_ORDERED", 1) != 0;
             if (ordered && (c->bs.d_fmask.reserve(total_px / ppw + 4096) || c->bs.d_fblk.reserve(1024)))
                 return fail(MI_DMRECON_EDEVICE, "hipMalloc(follow-up masks) failed");
-            D->optimize(S, 1, waves, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr, c->bs.d_results.p, n_thr_p,
-                        0u, plain_min, 0xFFFFFFFFu, r, c->d_counters, nullptr, nullptr, ordered ? nullptr : fl[0], fcnt, fseg, 0u, ordered ? c->bs.d_fmask.p : nullptr);
-            if (ordered) mi_launch_follow_compact(S, c->bs.d_fmask.p, n_thr_p, plain_min, 0xFFFFFFFFu, ppw, 64u / ppw, c->bs.d_fblk.p, fl[0], fcnt);
+            /* follow-up list k of this round, as the list a launch continues / the list it leaves */
+            auto continues = [&](MiOptLaunch& l, int k) { l.follow.in = fl[k]; l.follow.in_n = fcnt + MI_FOLLOW_SEGS * k; l.follow.seg_in = (k == 0 && ordered) ? 0u : fseg; };
+            auto leaves = [&](MiOptLaunch& l, int k) { l.follow.out = fl[k]; l.follow.out_n = fcnt + MI_FOLLOW_SEGS * k; };
+            /* the first attempts, in the FAST kernel: list 0 for the rest -- appended to, or (ordered) compacted from the masks */
+            MiOptLaunch first = thr;
+            first.follow.seg = fseg;
+            leaves(first, 0);
+            if (ordered) { first.follow.out = nullptr; first.follow.mask = c->bs.d_fmask.p; }
+            if (int rc = run(first, MI_OPT_FAST, waves)) return rc;
+            if (ordered) mi_launch_follow_compact(S, first, c->bs.d_fmask.p, ppw, 64u / ppw, c->bs.d_fblk.p, fl[0], fcnt);
+            /* the follow-up launches look at their own lists only (empty if the first launch did not act) */
+            MiOptLaunch next = thr;
+            next.min_work = 0; next.follow.seg = fseg;
+            /* ... what list k holds, all the attempts its entries have left in a row */
+            auto rest = [&](int k, unsigned grid) -> int { MiOptLaunch l = next; continues(l, k); ++n_launch; return run(l, MI_OPT_LOOP, grid); };
             if (SINGLE_FOLLOW) {
                 /* every further attempt as a launch of its own over the entries the reference's rule still asks one of (about
                  * a fifth, a thirtieth, ... of the list), again ONE attempt per entry: no chain of attempts is live across an
@@ -2209,28 +2236,17 @@ int BatchRun::bulk_rounds(bool& to_tail) {
                 for (int k = 0; k < n_single; ++k, div *= 4) {
                     /* MI_DMRECON_FAST_FOLLOW=<n>: the first n follow-up launches run the FAST kernel too (second attempts rarely need a
                      * view selection; the ones that do are abandoned again and go on to the next list) */
-                    D->optimize(S, k < FAST_FOLLOW ? 2 : 1, std::max(64u, waves / div), c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr,
-                                c->bs.d_results.p, n_thr_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters, fl[k], fcnt + MI_FOLLOW_SEGS * k, fl[k + 1], fcnt + MI_FOLLOW_SEGS * (k + 1), fseg,
-                                (k == 0 && ordered) ? 0u : fseg, nullptr);
+                    MiOptLaunch l = next;
+                    continues(l, k); leaves(l, k + 1);
+                    if (int rc = run(l, k < FAST_FOLLOW ? MI_OPT_FAST : MI_OPT_SINGLE, std::max(64u, waves / div))) return rc;
                     ++n_launch;
                 }
-                if (n_single == 4 && FAST_FOLLOW > 0) {
-                    /* an entry abandoned by FAST launches can have attempts left after the four single-attempt launches: what the
-                     * last of them appended (to the first list's buffer, consumed long ago) runs its remaining attempts in a row */
-                    D->optimize(S, 1, 64u, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr,
-                                c->bs.d_results.p, n_thr_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters, fl[4], fcnt + MI_FOLLOW_SEGS * 4, nullptr, nullptr, fseg, fseg, nullptr);
-                    ++n_launch;
-                }
-                if (n_single < 4) {
-                    D->optimize(S, 1, std::max(64u, waves / div), c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr,
-                                c->bs.d_results.p, n_thr_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters, fl[n_single], fcnt + MI_FOLLOW_SEGS * n_single, nullptr, nullptr, fseg, fseg, nullptr);
-                    ++n_launch;
-                }
-            } else {
-                D->optimize(S, 1, std::max(1u, waves / 4), c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work.p, nullptr,
-                            c->bs.d_results.p, n_thr_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters, fl[0], fcnt, nullptr, nullptr, fseg, fseg, nullptr);
-                ++n_launch;
+                /* an entry abandoned by FAST launches can have attempts left after the four single-attempt launches: what the
+                 * last of them appended (to the first list's buffer, consumed long ago) runs its remaining attempts in a row */
+                if (n_single == 4 && FAST_FOLLOW > 0) if (int rc = rest(4, 64u)) return rc;
+                if (n_single < 4) if (int rc = rest(n_single, std::max(64u, waves / div))) return rc;
             }
+            else if (int rc = rest(0, std::max(1u, waves / 4))) return rc;
         }
         ev.end(S);
         ++n_launch;
@@ -2241,17 +2257,14 @@ int BatchRun::bulk_rounds(bool& to_tail) {
             /* (the latency list can jump from nothing to a few hundred entries per view in one round, when the views of a batch
              * hand over together: a grid sized from the last list the host has seen would leave a thousand wavefronts striding
              * over it -- measured: 8 ms for such a round in a 200-view batch.  Wavefronts without an entry end at once.) */
-            const unsigned lat_grid = std::min(std::max(std::max(4u * known_lat, (unsigned)nj * std::min(handover, 1024u)), 4096u), 32768u);
-            D->optimize(S, 16, lat_grid, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, c->bs.d_work2.p,
-                        nullptr, c->bs.d_results2.p, n_lat_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters, nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr);
+            if (int rc = run(lat, MI_OPT_LATENCY, std::min(std::max(std::max(4u * known_lat, (unsigned)nj * std::min(handover, 1024u)), 4096u), 32768u))) return rc;
             ev.end(S);
             ++n_launch;
         }
         ev.begin(S, EventLog::SWEEP, 0);
-        if (spec) mi_launch_apply_spec(S, std::min((std::max(3u * known_thr, 16384u) + 255) / 256, 768u), c->bs.d_jobs.p, c->bs.d_work.p, c->bs.d_spec.p,
-                                       c->bs.d_follow.p, c->bs.d_round_items.p + r, n_thr_p, 0u, 0u, spec_cap, r, c->d_counters);
-        if (need_plain) mi_launch_apply(S, std::min((est + 255) / 256, 2048u), c->bs.d_jobs.p, c->bs.d_work.p, c->bs.d_results.p, n_thr_p, 0u, plain_min, 0xFFFFFFFFu, r, c->d_counters);
-        if (any_lat) mi_launch_apply(S, std::min((std::max(2u * known_lat, 1024u) + 255) / 256, 4096u), c->bs.d_jobs.p, c->bs.d_work2.p, c->bs.d_results2.p, n_lat_p, 0u, 0u, 0xFFFFFFFFu, r, c->d_counters);
+        if (spec) { sp.grid_blocks = std::min((std::max(3u * known_thr, 16384u) + 255) / 256, 768u); mi_launch_apply_spec(S, rb, sp); }
+        if (need_plain) mi_launch_apply(S, rb, thr, std::min((est + 255) / 256, 2048u));
+        if (any_lat) mi_launch_apply(S, rb, lat, std::min((std::max(2u * known_lat, 1024u) + 255) / 256, 4096u));
         ev.end(S);
         const int slot = r & 1;
         TailPoll& P = c->bs.h_poll[slot];
@@ -2366,12 +2379,13 @@ int BatchRun::tail_rounds(bool& to_front) {
         /* Speculative attempts (workgroups of four wavefronts) buy latency -- for a call that has the GPU to itself or
          * shares it with one other.  Next to the bulk rounds of several other calls the small form (one wavefront per
          * workgroup, 168 registers, 7 KB of LDS) is placed without draining a CU first and takes less from them. */
-        const bool speculative = tail_known <= SPEC_MAX && active.count() <= 2;
+        MiTailLaunch t;
+        t.grid_blocks = grid; t.round_work = c->bs.d_round_work.p; t.speculative = tail_known <= SPEC_MAX && active.count() <= 2;
         for (unsigned k = 0; k < MI_TAIL_CHUNK; ++k, ++round) {
             const bool timed = (stats != nullptr || trace) && k % TIMED_EVERY == 0;
             if (timed) ev.begin(S, EventLog::TAIL, k);            /* k -> entries after the read-back */
-            D->tail(S, grid, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, wcur, rcur, wnext, rnext, c->bs.d_round_work.p, round,
-                    c->d_counters, speculative);
+            t.prev_work = wcur; t.prev_results = rcur; t.work = wnext; t.results = rnext; t.round = round;
+            D->tail(S, base, t);
             if (timed) ev.end(S);
             std::swap(wcur, wnext); std::swap(rcur, rnext);
         }
@@ -2546,21 +2560,15 @@ int BatchRun::front_rounds() {
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 6 * (size_t)nj * sizeof(unsigned), S));                          /* sizes, statistics, team counts */
     HIP_TRY(hipMemsetAsync(d_resume, 0, 2 * (size_t)nj * sizeof(unsigned long long), S));
     front_first_round = round;
-    const unsigned spin_ticks = [] { const char* e = std::getenv("MI_DMRECON_TEAM_WAIT_US"); return 100u * (e ? (unsigned)std::max(1, std::atoi(e)) : MI_TEAM_WAIT_US); }();
+    const unsigned spin_ticks = 100u * (unsigned)std::max(1L, env_or("MI_DMRECON_TEAM_WAIT_US", MI_TEAM_WAIT_US));
+    MiFrontLaunch fr;
     /* test hook, MI_DMRECON_DEBUG_FRONT_FAULT=<member>[:<round>]: that member of every team vanishes at that round of its view */
-    const int fault = [] {
-        int f = -1;
-        if (const char* e = std::getenv("MI_DMRECON_DEBUG_FRONT_FAULT")) if (*e) {
-            const char* colon = std::strchr(e, ':');
-            f = (std::atoi(e) & 0xFF) | ((colon ? std::max(0, std::atoi(colon + 1)) & 0xFFFF : 0) << 8);
-        }
-        /* test hook, MI_DMRECON_DEBUG_TEAM_WT=1: the teams behave as if their members had been found on several XCDs */
-        if (const char* e = std::getenv("MI_DMRECON_DEBUG_TEAM_WT")) {
-            if (std::atoi(e) == 1) f = (f < 0 ? 0xFF : f) | (1 << 24);
-            if (std::atoi(e) == 2) f = (f < 0 ? 0xFF : f) | (1 << 25);       /* 2: exchanges through memory even within one XCD (A/B) */
-        }
-        return f;
-    }();
+    if (const char* e = std::getenv("MI_DMRECON_DEBUG_FRONT_FAULT")) if (*e) {
+        const char* colon = std::strchr(e, ':');
+        fr.debug.vanish_member = std::atoi(e); fr.debug.vanish_round = colon ? std::max(0, std::atoi(colon + 1)) : 0;
+    }
+    /* test hook, MI_DMRECON_DEBUG_TEAM_WT=1: the teams behave as if found on several XCDs; 2: they exchange through memory even within one XCD (A/B) */
+    fr.debug.write_through = env_or("MI_DMRECON_DEBUG_TEAM_WT", 0) == 1; fr.debug.exchange_through_memory = env_or("MI_DMRECON_DEBUG_TEAM_WT", 0) == 2;
     std::unique_ptr<TeamToken> token;
     if (front_team > 1) {
         token.reset(new TeamToken(c->device));
@@ -2588,8 +2596,7 @@ int BatchRun::front_rounds() {
      * engine (profiles/r5_ab_experiments.txt).  MI_DMRECON_FRONT_ORDER=0: index order. */
     const unsigned* d_order = nullptr;
     {
-        const char* e = std::getenv("MI_DMRECON_FRONT_ORDER");
-        if ((!e || std::atoi(e) != 0) && nj > 1 && view_filled.size() == (size_t)nj) {
+        if (env_or("MI_DMRECON_FRONT_ORDER", 1) != 0 && nj > 1 && view_filled.size() == (size_t)nj) {
             front_order.resize((size_t)nj);
             for (int j = 0; j < nj; ++j) front_order[j] = (unsigned)j;
             auto empty_px = [&](unsigned a) { return (long long)jobs[a].w * jobs[a].h - (long long)view_filled[a]; };
@@ -2626,8 +2633,7 @@ int BatchRun::front_rounds() {
     sparse = false; sparse_overflow = false; emit_order.clear(); emit_seen = 0; sparse_done_end = 0;
     snapped.assign((size_t)nj, 0);
     {
-        const char* e = std::getenv("MI_DMRECON_SPARSE_MAPS");
-        const int min_views = e ? std::atoi(e) : MI_MERGE_SMALL_CALL;
+        const int min_views = (int)env_or("MI_DMRECON_SPARSE_MAPS", MI_MERGE_SMALL_CALL);
         if (h_done && min_views > 0 && nj >= min_views && sparse_r0 > 0) {
             bool normal = false;
             for (int i = 0; i < n_refs; ++i) if (maps[i].normal) normal = true;
@@ -2653,7 +2659,7 @@ int BatchRun::front_rounds() {
             if (ok && bs.d_sparse_count.reserve(1)) ok = false;
             if (ok) {
                 sparse_cap = (unsigned)(bs.h_sparse_cap / sparse_stride);
-                if (const char* dc = std::getenv("MI_DMRECON_DEBUG_SPARSE_CAP")) sparse_cap = std::min(sparse_cap, (unsigned)std::max(1, std::atoi(dc)));   /* test hook */
+                sparse_cap = (unsigned)std::max(1L, std::min((long)sparse_cap, env_or("MI_DMRECON_DEBUG_SPARSE_CAP", (long)sparse_cap)));   /* test hook */
                 for (int j = 0; j < nj; ++j) bs.h_emit_end[j] = 0xFFFFFFFFu;
                 HIP_TRY(hipMemsetAsync(bs.d_sparse_count.p, 0, sizeof(unsigned), S));     /* (before the front kernel, on its stream) */
                 sparse = true;
@@ -2665,15 +2671,19 @@ int BatchRun::front_rounds() {
     /* the first launch deals the last tail round's list out to the views and runs them (as teams, if any); should the
      * teams give up (a member found no compute unit in time: something else holds them), a second launch takes every
      * unfinished view from the round it stopped in, one workgroup per view */
+    fr.n_jobs = nj; fr.list = wcur; fr.list_results = rcur; fr.list_n = c->bs.d_round_work.p + (round - 1);
+    fr.work[0] = wnext; fr.results[0] = rnext; fr.work[1] = wcur; fr.results[1] = rcur;
+    fr.job_off = d_off; fr.job_count = d_cnt; fr.job_stats = d_stats; fr.first_round = round; fr.max_rounds = max_round;
+    fr.job_resume = d_resume; fr.team_filled = d_filled; fr.spin_ticks = spin_ticks; fr.n_xcd = std::max(1, c->n_cus / 32); fr.host_done = h_done; fr.job_order = d_order;
+    if (front_team > 1) {
+        fr.team.size = front_team; fr.team.grid_blocks = front_grid; fr.team.mail = c->bs.d_front_mail.p; fr.team.flags = c->bs.d_front_flags.p; fr.team.block_map = c->bs.d_front_map.p;
+    }
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool again = attempt == 1;
+        /* the second launch: no teams, no test hooks; the views go on where the first one's record says, and record anew */
+        if (again) { fr.team = MiFrontTeam(); fr.debug = MiFrontDebug(); fr.job_start = d_resume; fr.job_resume = d_resume + nj; }
         ev.begin(S, EventLog::FRONT, tail_known);
-        D->front(S, nj, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, ds, wcur, rcur, c->bs.d_round_work.p + (round - 1),
-                 wnext, rnext, wcur, rcur, d_off, d_cnt, d_stats, round, max_round, c->d_counters,
-                 again ? 1 : front_team, (!again && front_team > 1) ? c->bs.d_front_mail.p : nullptr,
-                 (!again && front_team > 1) ? c->bs.d_front_flags.p : nullptr,
-                 again ? d_resume : nullptr, again ? d_resume + nj : d_resume, d_filled, spin_ticks, again ? -1 : fault,
-                 std::max(1, c->n_cus / 32), h_done, (!again && front_team > 1) ? c->bs.d_front_map.p : nullptr, front_grid, d_order);
+        D->front(S, base, fr);
         ev.end(S);
         ++n_launch;
         if (h_done) {
@@ -2777,8 +2787,9 @@ int BatchRun::snapshot_views() {
 int BatchRun::emit_view(int j) {
     streamed[j] = 1; ++n_streamed;
     hipStream_t S2 = c->stream2;
-    mi_launch_emit_changed(S2, c->bs.d_maps.p, c->bs.d_imaps.p, total_px, jobs[j].pix_off, (size_t)jobs[j].w * jobs[j].h, sparse_r0,
-                           (unsigned)j, sparse_stride, c->bs.d_sparse_count.p, sparse_cap, c->bs.h_sparse);
+    MiEmitLaunch em;
+    em.r0 = sparse_r0; em.view = (unsigned)j; em.stride = sparse_stride; em.d_count = c->bs.d_sparse_count.p; em.cap = sparse_cap; em.out = c->bs.h_sparse;
+    mi_launch_emit_changed(S2, c->bs.d_maps.p, c->bs.d_imaps.p, total_px, jobs[j].pix_off, (size_t)jobs[j].w * jobs[j].h, em);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&c->bs.h_emit_end[emit_order.size()], c->bs.d_sparse_count.p, sizeof(unsigned), hipMemcpyDeviceToHost, S2));
     emit_order.push_back(j);
@@ -3042,7 +3053,7 @@ static int reconstruct_batch(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, i
     PatientWaits patient(n_refs >= MI_MERGE_SMALL_CALL);
     BatchRun B;
     B.c = c; B.st = st; B.n_refs = n_refs; B.ref_views = ref_views; B.maps = maps; B.progress = progress;
-    B.status_out = status_out; B.stats = stats; B.D = mi_device_api(st->filterWidth); B.ds = dev_settings(st); B.S = c->stream;
+    B.status_out = status_out; B.stats = stats; B.D = mi_device_api(st->filterWidth); B.base.st = dev_settings(st); B.S = c->stream;
     B.trace = std::getenv("MI_DMRECON_TRACE") != nullptr; B.t_begin = B.t_mark = now_ms();
     B.ev.c = c; B.active_call = &active_call;
     std::memset(&B.hc, 0, sizeof(B.hc));
@@ -3293,14 +3304,17 @@ static int mi_dmrecon_patch_optimize_impl(mi_dmrecon_ctx* c, const mi_dmrecon_se
     HIP_TRY(hipMemcpyAsync(c->bs.d_work.p, ent.data(), n * sizeof(DevEntry), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->bs.d_hyp.p, hy.data(), n * sizeof(DevHyp), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, MI_COUNTER_BYTES, c->stream));
-    /* lanes_per_view = 16 runs the hook through the latency layout, anything else through the throughput layout */
-    const int lpv = lanes_per_view == 16 ? 16 : 1;
-    if (lpv == 16 && st->nrReconNeighbors > 8)
+    /* lanes_per_view = 16 runs the hook through the latency layout, anything else through the throughput layout's general kernel */
+    const bool latency = lanes_per_view == 16;
+    if (latency && st->nrReconNeighbors > 8)
         return fail(MI_DMRECON_EINVAL, "more than eight local views run in the throughput layout only (lanes_per_view = 1)");
-    const unsigned ppw = lpv == 16 ? 1u : patches_per_wave(st);
-    D.optimize(c->stream, lpv, ((unsigned)n + ppw - 1) / ppw, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, dev_settings(st),
-               c->bs.d_work.p, c->bs.d_hyp.p, c->bs.d_results.p, nullptr, (unsigned)n, 0u, 0xFFFFFFFFu, 0, c->d_counters,
-               nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr);
+    const unsigned ppw = latency ? 1u : patches_per_wave(st);
+    MiLaunchBase base;
+    base.jobs = c->bs.d_jobs.p; base.views = c->sc->d_views.p; base.lut = c->sc->d_lut; base.st = dev_settings(st); base.counters = c->d_counters;
+    MiOptLaunch l;
+    l.form = latency ? MI_OPT_LATENCY : MI_OPT_SINGLE; l.grid_blocks = ((unsigned)n + ppw - 1) / ppw; l.n_work = (unsigned)n;
+    l.work = c->bs.d_work.p; l.hyp = c->bs.d_hyp.p; l.results = c->bs.d_results.p;
+    if (D.optimize(c->stream, base, l)) return fail(MI_DMRECON_EDEVICE, "internal: no kernel for the hook's launch");
     HIP_TRY(hipGetLastError());
     std::vector<DevResult> res(n); std::vector<uint32_t> resx(2 * (size_t)n, 0xFFFFFFFFu);
     HIP_TRY(hipMemcpyAsync(res.data(), c->bs.d_results.p, n * sizeof(DevResult), hipMemcpyDeviceToHost, c->stream));
@@ -3349,8 +3363,11 @@ static int mi_dmrecon_patch_eval_impl(mi_dmrecon_ctx* c, const mi_dmrecon_settin
     HIP_TRY(hipMemsetAsync(diout.p, 0, 2 * G * sizeof(int32_t), c->stream));
     HIP_TRY(hipMemcpyAsync(c->bs.d_jobs.p, dj.data(), sizeof(DevJob), hipMemcpyHostToDevice, c->stream));
     float* d_master = dout.p; float* d_ncc = dout.p + 5; float* d_col = d_ncc + G; float* d_der = d_col + (size_t)G * NS3;
-    D.patch_eval(c->stream, c->bs.d_jobs.p, c->sc->d_views.p, c->sc->d_lut, dev_settings(st), x, y, depth, dzI, dzJ,
-                         d_master, d_ncc, diout.p, d_col, d_der, diout.p + G);
+    MiLaunchBase base;
+    base.jobs = c->bs.d_jobs.p; base.views = c->sc->d_views.p; base.lut = c->sc->d_lut; base.st = dev_settings(st);
+    MiEvalLaunch ev;
+    ev.x = x; ev.y = y; ev.depth = depth; ev.dzI = dzI; ev.dzJ = dzJ; ev.master = d_master; ev.ncc = d_ncc; ev.ok = diout.p; ev.col = d_col; ev.deriv = d_der; ev.level = diout.p + G;
+    D.patch_eval(c->stream, base, ev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(master, d_master, 5 * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(ncc, d_ncc, G * 4, hipMemcpyDeviceToHost, c->stream));

@@ -1,7 +1,8 @@
 """Generates tests/golden/round_counters.json: the work counters of mi_dmrecon_stats -- totals and the per-kernel arrays -- that
 the library reports for scenes G1 (views 0-4), H1 (views 0-8) and the mixed-size scene M1, by default and under the switches
 that force the other round plans.  Run on an MI355X with the build whose counts are to be pinned (the commit before the work
-counters were striped and k_generate claimed its list slots per strip of tiles):
+counters were striped and k_generate claimed its list slots per strip of tiles; the forms of the follow-up launches and the
+eight-slot case: the commit before the launchers took descriptors, which reproduced every older entry):
 
     python tests/golden/make_golden_round_counters.py [output file, default tests/golden/round_counters.json]
 
@@ -35,9 +36,22 @@ SWITCHES = {
     "two_launches_loop": {"MI_DMRECON_VIEW_HANDOVER": None, "MI_DMRECON_ONE_LAUNCH": "0", "MI_DMRECON_SPEC_ROUNDS": "0", "MI_DMRECON_SINGLE_FOLLOW": "0"},
     "all_speculative": {"MI_DMRECON_VIEW_HANDOVER": None, "MI_DMRECON_SPEC_ROUNDS": "1000000"},
 }
-# scene -> (scale, reference views, MI_DMRECON_VIEW_HANDOVER of the "handover" case)
-SCENES = {"g1": (0, [0, 1, 2, 3, 4], "150"), "h1": (0, list(range(9)), "60"), "m1": (0, [0, 1, 4], "150"), "m1_scale1": (1, [2], "150")}
-CASES = [(s, w) for s in SCENES for w in SWITCHES]
+# the forms of the two-launch plan's follow-up launches that no other case selects: the first two follow-ups in the FAST kernel, the
+# first follow-up list appended by atomics instead of compacted in list order, one list for all XCDs instead of a segment each
+TWO_LAUNCHES = SWITCHES["two_launches"]
+SWITCHES["fast_follow"] = dict(TWO_LAUNCHES, MI_DMRECON_FAST_FOLLOW="2")
+SWITCHES["unordered"] = dict(TWO_LAUNCHES, MI_DMRECON_FOLLOW_ORDERED="0")
+SWITCHES["one_list"] = dict(TWO_LAUNCHES, MI_DMRECON_FOLLOW_SEGMENTS="0")
+SAME_MAPS_AS_TWO_LAUNCHES = ("fast_follow", "unordered", "one_list")
+# scene -> (scale, reference views, MI_DMRECON_VIEW_HANDOVER of the "handover" case, settings other than the defaults)
+SCENES = {"g1": (0, [0, 1, 2, 3, 4], "150", {}), "h1": (0, list(range(9)), "60", {}), "m1": (0, [0, 1, 4], "150", {}),
+          "m1_scale1": (1, [2], "150", {}),
+          # the eight-slot layout (nrReconNeighbors > 4) through the follow-up launches: the two-launch plan only.  (With eight
+          # neighbours H1's lists are short: at 40 entries every view hands over at once and neither kernel of the plan runs, at 20
+          # most rounds run it and the views still end in the eight-slot latency layout and the front kernel.)
+          "h1_k8": (0, list(range(9)), "20", {"nrReconNeighbors": 8})}
+ONLY = {"h1_k8": ("two_launches",)}
+CASES = [(s, w) for s in SCENES for w in ONLY.get(s, SWITCHES)]
 
 
 def load_scene_data(name):
@@ -61,12 +75,12 @@ def counters_of(stats):
 def measure(ctx, scene_name, switch_name, want_maps=False):
     """The counters of one case on a context that holds the scene; the environment is put back afterwards."""
     from mve_amd import api
-    scale, refs, handover = SCENES[scene_name]
+    scale, refs, handover, settings = SCENES[scene_name]
     env = {k: (handover if v is None else v) for k, v in SWITCHES[switch_name].items()}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        maps = ctx.reconstruct(api.Settings(scale=scale), refs, want_views=True)
+        maps = ctx.reconstruct(api.Settings(scale=scale, **settings), refs, want_views=True)
     finally:
         for k, v in old.items():
             if v is None:

@@ -206,6 +206,27 @@ def test_every_build_switch_is_documented():
     assert tested == named, (sorted(tested - named), sorted(named - tested))
 
 
+def test_launchers_take_descriptors_not_long_argument_lists():
+    """No launcher of mve_amd/csrc/dmrecon_device.h -- a function-pointer member of MiDeviceApi or an mi_launch_* function --
+    has more than eight parameters: what a launch needs beyond that goes into a descriptor struct whose defaults mean "not
+    used", so that no call site spells out a row of positional nulls again.  mi_launch_round_report (five array / count pairs and
+    three outputs, four call sites that differ in which pairs they give) is the one exemption."""
+    src = open(os.path.join(ROOT, "mve_amd", "csrc", "dmrecon_device.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    decls = re.findall(r"\(\s*\*\s*(\w+)\s*\)\s*\(([^()]*)\)\s*;", src) + re.findall(r"\b(mi_launch_\w+)\s*\(([^()]*)\)\s*;", src)
+    names = [n for n, _ in decls]
+    assert len(names) >= 18 and {"optimize", "front", "tail", "generate", "optimize_spec", "patch_eval", "mi_launch_apply"} <= set(names), names
+    for name, params in decls:
+        if name != "mi_launch_round_report":
+            assert params.count(",") + 1 <= 8, (name, params.count(",") + 1)
+
+
+def test_the_kernel_form_is_named_not_inferred():
+    """The launcher of k_optimize is told the kernel form (MiOptForm); the parameter it used to infer it from is gone."""
+    for f in ("dmrecon_device.h", "dmrecon_device.hip"):
+        assert "lanes_per_view" not in open(os.path.join(ROOT, "mve_amd", "csrc", f)).read(), f
+
+
 def test_bench_call_plan():
     """bench.py: how K timed steps become library calls (pure host logic)."""
     import importlib.util
