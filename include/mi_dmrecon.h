@@ -430,6 +430,51 @@ int  mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_
 /* Frees the sets, streams and result buffers.  Destroy it before its context. */
 void mi_dmrecon_match_destroy(mi_dmrecon_match* m);
 
+/* ---- ... and what sfmrecon does with the matches of a pair: RANSAC for the fundamental matrix ------------------------ */
+
+/* One sfm::RansacFundamental::estimate (libs/sfm/ransac_fundamental.cc:26-58) with its random draws made by the caller. */
+typedef struct mi_dmrecon_ransac_job {
+    int32_t n_matches;          /* >= 8 */
+    int32_t n_iterations;       /* >= 1 */
+    const double*  matches;     /* n_matches x 4: p1.x p1.y p2.x p2.y (sfm::Correspondence2D2D) */
+    const int32_t* samples;     /* n_iterations x 8 indices into matches, distinct within a row */
+    double  threshold;          /* RansacFundamental::Options::threshold; compared squared */
+    int32_t inliers_to_beat;    /* result->inliers.size() on entry; a hypothesis wins only with MORE */
+} mi_dmrecon_ransac_job;
+
+/* n_jobs estimates in three launches.  Per iteration: the 8-point solve of its eight sampled matches
+ * (fundamental_8_point, libs/sfm/fundamental.cc:77-110: the right singular vector of the 8 x 9 system for its smallest
+ * singular value; the points are NOT normalised, as in the reference's RANSAC path), rank 2 enforced
+ * (enforce_fundamental_constraints, :112-126), and the number of matches with sampson_distance(F, m) < threshold^2
+ * (:224-247; find_inliers, ransac_fundamental.cc:93-105).  The winner of a job is the FIRST iteration whose count is strictly
+ * greater than every count before it and greater than inliers_to_beat (ransac_fundamental.cc:38-57).
+ * Outputs: best_iteration [n_jobs] (-1: nothing beat inliers_to_beat; the job's other outputs are then left untouched);
+ * fundamental [9 n_jobs], row-major, the winning hypothesis as computed (not re-estimated from its inliers); n_inliers
+ * [n_jobs]; inliers[j]: room for n_matches indices, written ascending.  Optional (NULL, or NULL per job):
+ * iteration_counts[j], n_iterations inlier counts, and iteration_F[j], n_iterations x 9.
+ * All arithmetic is double.  A hypothesis whose F is not finite has count 0.
+ * Domain: finite coordinates.  NO bit-parity with the reference is claimed: the reference is built with
+ * -funsafe-math-optimizations and uses an iterative SVD of its own, this library a Jacobi iteration; both compute the same
+ * singular vectors to rounding, so F agrees to the conditioning of the sample, and the inlier sets agree except for matches
+ * whose distance lies within rounding of the threshold.  The inlier test is  numerator < threshold^2 * denominator  (no
+ * division); a zero denominator is "not an inlier" in both forms.
+ * MI_DMRECON_EINVAL, naming the job, before anything is allocated or launched: n_matches < 8; n_iterations < 1; a null
+ * pointer; a negative inliers_to_beat; a threshold that is NaN; a sample index outside [0, n_matches) or repeated within
+ * its row; a call of more than 2^30 iterations or matches, or of more than 2^24 - 1 tiles of 128 iterations x 256 matches.
+ * The buffers belong to the context and grow only.  Contexts forked from one parent (mi_dmrecon_ctx_fork) run their calls
+ * on their own streams, one host thread per context. */
+int mi_dmrecon_ransac_fundamental(mi_dmrecon_ctx* ctx, int32_t n_jobs, const mi_dmrecon_ransac_job* jobs,
+    int32_t* best_iteration,        /* per job; -1: nothing beat inliers_to_beat, the job's other outputs untouched */
+    double*  fundamental,           /* 9 per job, row-major, the winning hypothesis as computed (not re-estimated) */
+    int32_t* n_inliers,             /* per job */
+    int32_t* const* inliers,        /* per job: room for n_matches indices, written ascending */
+    int32_t* const* iteration_counts,   /* optional (NULL, or NULL per job): n_iterations inlier counts */
+    double*  const* iteration_F);       /* optional likewise: n_iterations x 9 */
+
+/* Solves (of the 8 x 9 system or of the 3 x 3 rank step) of this context's calls so far that were still rotating after
+ * the last Jacobi sweep the kernel allows (30); their hypotheses were kept as they stood.  0 is the expected value. */
+long long mi_dmrecon_ransac_sweep_capped(mi_dmrecon_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ EXPORTS = [
     "mi_dmrecon_patch_optimize", "mi_dmrecon_patch_eval", "mi_dmrecon_pointset",
     "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
+    "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
 ]
 
 # the test hooks of include/mi_dmrecon_debug.h (EXPORTS is the drop-in boundary, include/mi_dmrecon.h, alone)
@@ -58,6 +59,7 @@ DEBUG_EXPORTS = [
 
 MATCH_SIFT, MATCH_SURF = 0, 1      # MI_DMRECON_MATCH_SIFT / _SURF: 128 unsigned dims / 64 signed dims
 MATCH_F32, MATCH_I16 = 0, 1        # MI_DMRECON_MATCH_F32 / _I16
+RANSAC_TILE, RANSAC_CHUNK = 128, 256   # mve_amd/csrc/ransac_device.h: iterations x matches of one workgroup of k_ransac_count
 
 
 class CCamera(ctypes.Structure):
@@ -99,6 +101,11 @@ class CMatchOptions(ctypes.Structure):
 
 class CMatchJob(ctypes.Structure):
     _fields_ = [("set_a", ctypes.c_int32), ("n_a", ctypes.c_int32), ("set_b", ctypes.c_int32), ("n_b", ctypes.c_int32)]
+
+
+class CRansacJob(ctypes.Structure):
+    _fields_ = [("n_matches", ctypes.c_int32), ("n_iterations", ctypes.c_int32), ("matches", ctypes.c_void_p),
+                ("samples", ctypes.c_void_p), ("threshold", ctypes.c_double), ("inliers_to_beat", ctypes.c_int32)]
 
 
 class CProgress(ctypes.Structure):
@@ -211,6 +218,10 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_match_pairs.argtypes = [vp, i32, ctypes.POINTER(CMatchOptions), i32, vp, vp, vp, vp]
         L.mi_dmrecon_match_destroy.argtypes = [vp]
         L.mi_dmrecon_match_destroy.restype = None
+    if hasattr(L, "mi_dmrecon_ransac_fundamental"):
+        L.mi_dmrecon_ransac_fundamental.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.mi_dmrecon_ransac_sweep_capped.argtypes = [vp]
+        L.mi_dmrecon_ransac_sweep_capped.restype = ctypes.c_longlong
     if hasattr(L, "mi_dmrecon_debug_match_get"):                                                             # test hooks
         ll = ctypes.c_longlong
         L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
@@ -673,6 +684,58 @@ class Context:
     def match_open(self, n_sets: int) -> "Matcher":
         """A matcher for ``n_sets`` descriptor sets on this context's device (mi_dmrecon_match_create)."""
         return Matcher(self, n_sets)
+
+    def ransac_fundamental(self, jobs, per_iteration: bool = False, out=None):
+        """sfm::RansacFundamental::estimate (libs/sfm/ransac_fundamental.cc:26-58) for a list of jobs in one call
+        (mi_dmrecon_ransac_fundamental).  A job is (matches (n, 4) float64 rows p1.x p1.y p2.x p2.y, samples (it, 8) int32
+        rows of distinct indices into the matches, threshold[, inliers_to_beat = 0]).  Returns per job a dict of
+        ``best_iteration`` (-1: no iteration had more than inliers_to_beat inliers), ``F`` (3, 3) and ``inliers`` (int32,
+        ascending), with ``per_iteration`` also ``counts`` (it,) and ``F_all`` (it, 3, 3).
+        ``out``: per job the caller's own (F (3, 3) float64, inliers (n,) int32) to write into, as the reference writes
+        into the Result it is given: a job without a winner leaves them as they were (without ``out``: NaN and empty)."""
+        if not hasattr(self._L, "mi_dmrecon_ransac_fundamental"):
+            raise RuntimeError("%s has no mi_dmrecon_ransac_fundamental: rebuild the library" % LIB_PATH)
+        n = len(jobs)
+        if n == 0:
+            return []
+        ms = [np.ascontiguousarray(j[0], np.float64).reshape(-1, 4) for j in jobs]
+        ss = [np.ascontiguousarray(j[1], np.int32).reshape(-1, 8) for j in jobs]
+        cj = (CRansacJob * n)(*[CRansacJob(len(m), len(s), m.ctypes.data, s.ctypes.data, float(j[2]), int(j[3]) if len(j) > 3 else 0)
+                                for j, m, s in zip(jobs, ms, ss)])
+        if out is None:
+            out = [(np.full((3, 3), np.nan), np.full(len(m), -1, np.int32)) for m in ms]
+        for (F, inl), m in zip(out, ms):
+            if F.dtype != np.float64 or F.size != 9 or inl.dtype != np.int32 or inl.size < len(m) \
+                    or not F.flags.c_contiguous or not inl.flags.c_contiguous:
+                raise ValueError("out: per job a contiguous (3, 3) float64 and an int32 array with room for every match")
+        best, n_inl = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+        F = np.zeros((n, 9))
+        for k, (Fk, _) in enumerate(out):
+            F[k] = Fk.ravel()
+        p_inl = (ctypes.c_void_p * n)(*[o[1].ctypes.data for o in out])
+        counts = [np.zeros(len(s), np.int32) for s in ss] if per_iteration else None
+        F_all = [np.zeros((len(s), 3, 3)) for s in ss] if per_iteration else None
+        p_counts = (ctypes.c_void_p * n)(*[a.ctypes.data for a in counts]) if per_iteration else None
+        p_F = (ctypes.c_void_p * n)(*[a.ctypes.data for a in F_all]) if per_iteration else None
+        rc = self._L.mi_dmrecon_ransac_fundamental(self._h, n, ctypes.cast(cj, ctypes.c_void_p), _ptr(best), _ptr(F), _ptr(n_inl),
+                                                   ctypes.cast(p_inl, ctypes.c_void_p),
+                                                   ctypes.cast(p_counts, ctypes.c_void_p) if per_iteration else None,
+                                                   ctypes.cast(p_F, ctypes.c_void_p) if per_iteration else None)
+        if rc < 0:
+            _raise(rc)
+        res = []
+        for k in range(n):
+            out[k][0][...] = F[k].reshape(out[k][0].shape)
+            r = dict(best_iteration=int(best[k]), F=out[k][0], inliers=out[k][1][:n_inl[k]])
+            if per_iteration:
+                r["counts"], r["F_all"] = counts[k], F_all[k]
+            res.append(r)
+        return res
+
+    @property
+    def ransac_sweep_capped(self) -> int:
+        """Jacobi solves of this context's ransac_fundamental calls so far that were cut off at the kernel's last sweep."""
+        return int(self._L.mi_dmrecon_ransac_sweep_capped(self._h))
 
 
 class Matcher:

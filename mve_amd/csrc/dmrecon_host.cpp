@@ -464,6 +464,8 @@ struct SceneStore {
     }
 };
 
+void mi_ransac_release(struct RansacState* s);   /* ransac_host.cpp */
+
 struct mi_dmrecon_ctx {
     int device = 0;
     int n_cus = 64;                          /* compute units (queried at creation) */
@@ -479,6 +481,7 @@ struct mi_dmrecon_ctx {
     DevBuf<uint8_t> d_stage2;
     int stage_flip = 0;
     BatchScratch bs;                         /* leased from the scene's pool for the duration of a call (ScratchLease) */
+    struct RansacState* ransac = nullptr;    /* buffers of mi_dmrecon_ransac_fundamental (ransac_host.cpp), made by its first call */
 };
 
 namespace {
@@ -1489,6 +1492,7 @@ void mi_dmrecon_ctx_destroy(mi_dmrecon_ctx* c) {
     if (c->stream2) (void)wait_stream(c->stream2);
     c->bs.release();
     c->d_stage.release(); c->d_stage2.release();
+    mi_ransac_release(c->ransac);
     if (c->d_counters) (void)hipFree(c->d_counters);
     (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -3590,3 +3594,4 @@ int mi_dmrecon_pointset(mi_dmrecon_ctx* c, const mi_dmrecon_camera* cam, int32_t
 /* for the other host sources of the library (fssr_host.cpp); not exported (exports.map) */
 int mi_host_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int mi_host_ctx_device(const mi_dmrecon_ctx* c) { return c ? c->device : -1; }
+RansacState** mi_host_ctx_ransac(mi_dmrecon_ctx* c) { return &c->ransac; }
