@@ -475,6 +475,46 @@ int mi_dmrecon_ransac_fundamental(mi_dmrecon_ctx* ctx, int32_t n_jobs, const mi_
  * the last Jacobi sweep the kernel allows (30); their hypotheses were kept as they stood.  0 is the expected value. */
 long long mi_dmrecon_ransac_sweep_capped(mi_dmrecon_ctx* ctx);
 
+/* ---- ... and where its descriptors come from: sfm::Sift (libs/sfm/sift.cc), detection and description of one image ---- */
+
+/* sfm::Sift::Options (libs/sfm/sift.h:48-109) without the two output switches; the reference's defaults are
+ * 3, 0, 4, -1 (meaning 0.02 / num_samples_per_octave), 10, 1.6, 0.5. */
+typedef struct mi_dmrecon_sift_options {
+    int32_t num_samples_per_octave, min_octave, max_octave;
+    float contrast_threshold, edge_ratio_threshold, base_blur_sigma, inherent_blur_sigma;
+} mi_dmrecon_sift_options;
+
+/* sfm::Sift::Keypoint (sift.h:120-130): position and sample within the octave's image */
+typedef struct mi_dmrecon_sift_keypoint {
+    int32_t octave;
+    float sample, x, y;
+} mi_dmrecon_sift_keypoint;
+
+/* Sift::set_image / set_float_image + Sift::process (sift.cc:42-165) for one image of w x h pixels with 1 or 3 interleaved
+ * channels, unsigned char (is_float = 0) or float.  All arithmetic is f32.  The results stay with the context until its next
+ * call; n_keypoints is what get_keypoints() would hold, n_descriptors what get_descriptors() would.  Keypoints come in the
+ * reference's order (octave, sample, y, x of the extremum), descriptors in keypoint order, then ascending orientation bin.
+ * The same input gives the same bytes on every run; NO bit-parity with the reference is claimed (its sums run in another
+ * order, and it is built with unsafe-math optimisations): positions, scales, orientations and descriptors agree to rounding,
+ * and a keypoint or orientation that passes one of its tests by less than rounding may be present on one side only.
+ * A keypoint whose Taylor solve is not a number is dropped (the reference would index an image with it).
+ * MI_DMRECON_EINVAL, naming the field, before anything is allocated or launched: min_octave < -1 or > max_octave ("Invalid
+ * octave range"), or more than 20 octaves; channels not 1 or 3; num_samples_per_octave outside 1 ... 32; w or h outside
+ * 1 ... 32767 (16383 with min_octave -1) or more than 2^28 pixels in the largest octave; sigmas that are not positive and
+ * finite; float pixels that are not finite; a blur whose radius ks = ceil(sigma * 2.884) exceeds 32 (the kernels' built-in
+ * maximum: num_samples_per_octave 1 ... 6 at the default sigmas need at most 32); an image that rescale_half_size_gaussian
+ * would refuse because a side is below 2 ("Invalid input image"), the half-size taken behind the last octave included.
+ * A negative contrast_threshold means 0.02 / num_samples_per_octave.  One upload, launches on the context's stream, one
+ * small download of the counts.  The buffers belong to the context and grow only; a fork (mi_dmrecon_ctx_fork) has its own,
+ * so every host thread can run its own images. */
+int mi_dmrecon_sift_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const void* pixels, int32_t is_float,
+                        int32_t w, int32_t h, int32_t channels, int32_t* n_keypoints, int32_t* n_descriptors);
+
+/* Copies the results of the context's last successful mi_dmrecon_sift_run: kp [n_keypoints]; xyso [n_descriptors x 4]:
+ * Descriptor::x, y (in pixels of the input image: 2^octave (x + 0.5) - 0.5, sift.cc:544-547), scale and orientation;
+ * desc [n_descriptors x 128].  Each of the three may be NULL.  MI_DMRECON_EINVAL without such a run. */
+int mi_dmrecon_sift_get(mi_dmrecon_ctx* ctx, mi_dmrecon_sift_keypoint* kp, float* xyso, float* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,7 @@ EXPORTS = [
     "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
     "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
+    "mi_dmrecon_sift_run", "mi_dmrecon_sift_get",
 ]
 
 # the test hooks of include/mi_dmrecon_debug.h (EXPORTS is the drop-in boundary, include/mi_dmrecon.h, alone)
@@ -106,6 +107,18 @@ class CMatchJob(ctypes.Structure):
 class CRansacJob(ctypes.Structure):
     _fields_ = [("n_matches", ctypes.c_int32), ("n_iterations", ctypes.c_int32), ("matches", ctypes.c_void_p),
                 ("samples", ctypes.c_void_p), ("threshold", ctypes.c_double), ("inliers_to_beat", ctypes.c_int32)]
+
+
+class CSiftOptions(ctypes.Structure):
+    """mi_dmrecon_sift_options = sfm::Sift::Options (libs/sfm/sift.h:48-109) without the output switches."""
+    _fields_ = [("num_samples_per_octave", ctypes.c_int32), ("min_octave", ctypes.c_int32), ("max_octave", ctypes.c_int32),
+                ("contrast_threshold", ctypes.c_float), ("edge_ratio_threshold", ctypes.c_float),
+                ("base_blur_sigma", ctypes.c_float), ("inherent_blur_sigma", ctypes.c_float)]
+
+
+SIFT_DEFAULTS = dict(num_samples_per_octave=3, min_octave=0, max_octave=4, contrast_threshold=-1.0, edge_ratio_threshold=10.0,
+                     base_blur_sigma=1.6, inherent_blur_sigma=0.5)                      # Sift::Options::Options (sift.h:225-236)
+SIFT_KEYPOINT = np.dtype([("octave", np.int32), ("sample", np.float32), ("x", np.float32), ("y", np.float32)])
 
 
 class CProgress(ctypes.Structure):
@@ -222,6 +235,9 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_ransac_fundamental.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.mi_dmrecon_ransac_sweep_capped.argtypes = [vp]
         L.mi_dmrecon_ransac_sweep_capped.restype = ctypes.c_longlong
+    if hasattr(L, "mi_dmrecon_sift_run"):
+        L.mi_dmrecon_sift_run.argtypes = [vp, ctypes.POINTER(CSiftOptions), vp, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.mi_dmrecon_sift_get.argtypes = [vp, vp, vp, vp]
     if hasattr(L, "mi_dmrecon_debug_match_get"):                                                             # test hooks
         ll = ctypes.c_longlong
         L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
@@ -731,6 +747,38 @@ class Context:
                 r["counts"], r["F_all"] = counts[k], F_all[k]
             res.append(r)
         return res
+
+    def sift(self, image, **options):
+        """sfm::Sift::set_image / set_float_image + process (libs/sfm/sift.cc) for one image on the GPU (mi_dmrecon_sift_run,
+        mi_dmrecon_sift_get).  ``image``: uint8 or float32, H x W or H x W x 3.  ``options``: the fields of Sift::Options
+        (SIFT_DEFAULTS).  Returns (keypoints, xyso, descriptors): a SIFT_KEYPOINT record array in the reference's order, and
+        per descriptor x, y, scale, orientation (n, 4) and the 128 values (n, 128), float32."""
+        if not hasattr(self._L, "mi_dmrecon_sift_run"):
+            raise RuntimeError("%s has no mi_dmrecon_sift_run: rebuild the library" % LIB_PATH)
+        unknown = set(options) - set(SIFT_DEFAULTS)
+        if unknown:
+            raise TypeError("sift: unknown options %s" % sorted(unknown))
+        img = np.asarray(image)
+        if img.dtype not in (np.uint8, np.float32):
+            raise ValueError("sift: image must be uint8 or float32, not %s" % img.dtype)
+        if img.ndim not in (2, 3):
+            raise ValueError("sift: image must be H x W or H x W x channels")
+        img = np.ascontiguousarray(img)
+        h, w = img.shape[:2]
+        channels = img.shape[2] if img.ndim == 3 else 1
+        o = dict(SIFT_DEFAULTS, **options)
+        opt = CSiftOptions(*[o[f] for f, _ in CSiftOptions._fields_])
+        n_kp, n_desc = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._L.mi_dmrecon_sift_run(self._h, ctypes.byref(opt), _ptr(img), int(img.dtype == np.float32), w, h, channels,
+                                         ctypes.byref(n_kp), ctypes.byref(n_desc))
+        if rc < 0:
+            _raise(rc)
+        kp = np.zeros(n_kp.value, SIFT_KEYPOINT)
+        xyso, desc = np.zeros((n_desc.value, 4), np.float32), np.zeros((n_desc.value, 128), np.float32)
+        rc = self._L.mi_dmrecon_sift_get(self._h, _ptr(kp), _ptr(xyso), _ptr(desc))
+        if rc < 0:
+            _raise(rc)
+        return kp, xyso, desc
 
     @property
     def ransac_sweep_capped(self) -> int:

@@ -465,6 +465,7 @@ struct SceneStore {
 };
 
 void mi_ransac_release(struct RansacState* s);   /* ransac_host.cpp */
+void mi_sift_release(struct SiftState* s);       /* sift_host.cpp */
 
 struct mi_dmrecon_ctx {
     int device = 0;
@@ -482,6 +483,7 @@ struct mi_dmrecon_ctx {
     int stage_flip = 0;
     BatchScratch bs;                         /* leased from the scene's pool for the duration of a call (ScratchLease) */
     struct RansacState* ransac = nullptr;    /* buffers of mi_dmrecon_ransac_fundamental (ransac_host.cpp), made by its first call */
+    struct SiftState* sift = nullptr;        /* buffers and last results of mi_dmrecon_sift_run (sift_host.cpp), likewise */
 };
 
 namespace {
@@ -1493,6 +1495,7 @@ void mi_dmrecon_ctx_destroy(mi_dmrecon_ctx* c) {
     c->bs.release();
     c->d_stage.release(); c->d_stage2.release();
     mi_ransac_release(c->ransac);
+    mi_sift_release(c->sift);
     if (c->d_counters) (void)hipFree(c->d_counters);
     (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -3595,3 +3598,4 @@ int mi_dmrecon_pointset(mi_dmrecon_ctx* c, const mi_dmrecon_camera* cam, int32_t
 int mi_host_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int mi_host_ctx_device(const mi_dmrecon_ctx* c) { return c ? c->device : -1; }
 RansacState** mi_host_ctx_ransac(mi_dmrecon_ctx* c) { return &c->ransac; }
+SiftState** mi_host_ctx_sift(mi_dmrecon_ctx* c) { return &c->sift; }
