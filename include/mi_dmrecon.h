@@ -515,6 +515,46 @@ int mi_dmrecon_sift_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt,
  * desc [n_descriptors x 128].  Each of the three may be NULL.  MI_DMRECON_EINVAL without such a run. */
 int mi_dmrecon_sift_get(mi_dmrecon_ctx* ctx, mi_dmrecon_sift_keypoint* kp, float* xyso, float* desc);
 
+/* ---- ... and sfm::Surf (libs/sfm/surf.cc), the other detector apps/sfmrecon runs per view ---- */
+
+/* sfm::Surf::Options (libs/sfm/surf.h:46-65) without the two output switches; the reference's defaults are 500, 0. */
+typedef struct mi_dmrecon_surf_options {
+    float contrast_threshold;
+    int32_t use_upright_descriptor;
+} mi_dmrecon_surf_options;
+
+/* sfm::Surf::Keypoint (surf.h:70-76): octave, sample within the octave, position in pixels of the input image */
+typedef struct mi_dmrecon_surf_keypoint {
+    int32_t octave;
+    float sample, x, y;
+} mi_dmrecon_surf_keypoint;
+
+/* Surf::set_image + Surf::process (surf.cc:48-138) for one image of w x h pixels with 1 or 3 interleaved unsigned char
+ * channels (3: the lightness (max + min + 1) >> 1).  The results stay with the context until its next SURF call and are
+ * independent of the SIFT results; n_keypoints is what get_keypoints() would hold, n_descriptors what get_descriptors()
+ * would.  Keypoints come in the reference's order (octave, sample, y, x of the extremum), descriptors in keypoint order.
+ * The same input gives the same bytes on every run.
+ * Parity.  The summed-area table, the filter sums and the 16 response maps are the reference's bit for bit when it is built
+ * without contraction and unsafe-math optimisations (each response is float(sum) * inv_karea, then dxx * dyy - 0.912f * dxy *
+ * dxy in single f32 operations); the localisation runs in f64 with the reference's expressions, the window sums and the
+ * descriptor bins are added in the reference's order.  What is NOT the reference's to the bit: atan2 (f64), sinf and cosf, so
+ * orientations agree to rounding and a descriptor sample whose rotated coordinate rounds the other way moves one pixel; a
+ * keypoint that passes one of the tests by less than rounding may be present on one side only.  No deviation in behaviour:
+ * the reference reads one map row above the first and below the last one while scanning for extrema (surf.cc:326-329 with
+ * :344-365) only for pixels of the zero border, which fail its first comparison; they are not tested here.
+ * An image too small for any response outside the border is no error: 0 keypoints.
+ * MI_DMRECON_EINVAL, naming the field, before anything is allocated or launched: channels not 1 or 3; w or h outside
+ * 1 ... 32767 or more than 2^28 pixels; a null pointer; a contrast_threshold that is not finite.  One upload, launches on
+ * the context's stream, one small download of the counts.  The buffers belong to the context and grow only; a fork
+ * (mi_dmrecon_ctx_fork) has its own, so every host thread can run its own images. */
+int mi_dmrecon_surf_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const uint8_t* pixels, int32_t w, int32_t h,
+                        int32_t channels, int32_t* n_keypoints, int32_t* n_descriptors);
+
+/* Copies the results of the context's last successful mi_dmrecon_surf_run: kp [n_keypoints]; xyso [n_descriptors x 4]:
+ * Descriptor::x, y, scale (1.2 / 9 of the filter width, surf.cc:497-498) and orientation; desc [n_descriptors x 64].  Each
+ * of the three may be NULL.  MI_DMRECON_EINVAL without such a run. */
+int mi_dmrecon_surf_get(mi_dmrecon_ctx* ctx, mi_dmrecon_surf_keypoint* kp, float* xyso, float* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@ EXPORTS = [
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
     "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
     "mi_dmrecon_sift_run", "mi_dmrecon_sift_get",
+    "mi_dmrecon_surf_run", "mi_dmrecon_surf_get",
 ]
 
 # the test hooks of include/mi_dmrecon_debug.h (EXPORTS is the drop-in boundary, include/mi_dmrecon.h, alone)
@@ -119,6 +120,15 @@ class CSiftOptions(ctypes.Structure):
 SIFT_DEFAULTS = dict(num_samples_per_octave=3, min_octave=0, max_octave=4, contrast_threshold=-1.0, edge_ratio_threshold=10.0,
                      base_blur_sigma=1.6, inherent_blur_sigma=0.5)                      # Sift::Options::Options (sift.h:225-236)
 SIFT_KEYPOINT = np.dtype([("octave", np.int32), ("sample", np.float32), ("x", np.float32), ("y", np.float32)])
+
+
+class CSurfOptions(ctypes.Structure):
+    """mi_dmrecon_surf_options = sfm::Surf::Options (libs/sfm/surf.h:46-65) without the output switches."""
+    _fields_ = [("contrast_threshold", ctypes.c_float), ("use_upright_descriptor", ctypes.c_int32)]
+
+
+SURF_DEFAULTS = dict(contrast_threshold=500.0, use_upright_descriptor=False)            # Surf::Options::Options (surf.h:161-168)
+SURF_KEYPOINT = SIFT_KEYPOINT
 
 
 class CProgress(ctypes.Structure):
@@ -238,6 +248,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(L, "mi_dmrecon_sift_run"):
         L.mi_dmrecon_sift_run.argtypes = [vp, ctypes.POINTER(CSiftOptions), vp, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.mi_dmrecon_sift_get.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "mi_dmrecon_surf_run"):
+        L.mi_dmrecon_surf_run.argtypes = [vp, ctypes.POINTER(CSurfOptions), vp, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.mi_dmrecon_surf_get.argtypes = [vp, vp, vp, vp]
     if hasattr(L, "mi_dmrecon_debug_match_get"):                                                             # test hooks
         ll = ctypes.c_longlong
         L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
@@ -776,6 +789,37 @@ class Context:
         kp = np.zeros(n_kp.value, SIFT_KEYPOINT)
         xyso, desc = np.zeros((n_desc.value, 4), np.float32), np.zeros((n_desc.value, 128), np.float32)
         rc = self._L.mi_dmrecon_sift_get(self._h, _ptr(kp), _ptr(xyso), _ptr(desc))
+        if rc < 0:
+            _raise(rc)
+        return kp, xyso, desc
+
+    def surf(self, image, **options):
+        """sfm::Surf::set_image + process (libs/sfm/surf.cc) for one image on the GPU (mi_dmrecon_surf_run, mi_dmrecon_surf_get).
+        ``image``: uint8, H x W or H x W x 3.  ``options``: the fields of Surf::Options (SURF_DEFAULTS).  Returns (keypoints,
+        xyso, descriptors): a SURF_KEYPOINT record array in the reference's order, and per descriptor x, y, scale, orientation
+        (n, 4) and the 64 values (n, 64), float32."""
+        if not hasattr(self._L, "mi_dmrecon_surf_run"):
+            raise RuntimeError("%s has no mi_dmrecon_surf_run: rebuild the library" % LIB_PATH)
+        unknown = set(options) - set(SURF_DEFAULTS)
+        if unknown:
+            raise TypeError("surf: unknown options %s" % sorted(unknown))
+        img = np.asarray(image)
+        if img.dtype != np.uint8:
+            raise ValueError("surf: image must be uint8, not %s" % img.dtype)
+        if img.ndim not in (2, 3):
+            raise ValueError("surf: image must be H x W or H x W x channels")
+        img = np.ascontiguousarray(img)
+        h, w = img.shape[:2]
+        channels = img.shape[2] if img.ndim == 3 else 1
+        o = dict(SURF_DEFAULTS, **options)
+        opt = CSurfOptions(float(o["contrast_threshold"]), int(bool(o["use_upright_descriptor"])))
+        n_kp, n_desc = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = self._L.mi_dmrecon_surf_run(self._h, ctypes.byref(opt), _ptr(img), w, h, channels, ctypes.byref(n_kp), ctypes.byref(n_desc))
+        if rc < 0:
+            _raise(rc)
+        kp = np.zeros(n_kp.value, SURF_KEYPOINT)
+        xyso, desc = np.zeros((n_desc.value, 4), np.float32), np.zeros((n_desc.value, 64), np.float32)
+        rc = self._L.mi_dmrecon_surf_get(self._h, _ptr(kp), _ptr(xyso), _ptr(desc))
         if rc < 0:
             _raise(rc)
         return kp, xyso, desc
