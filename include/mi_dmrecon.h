@@ -555,6 +555,107 @@ int mi_dmrecon_surf_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt,
  * of the three may be NULL.  MI_DMRECON_EINVAL without such a run. */
 int mi_dmrecon_surf_get(mi_dmrecon_ctx* ctx, mi_dmrecon_surf_keypoint* kp, float* xyso, float* desc);
 
+/* ---- ... and what the incremental bundler runs after every view: sfm::ba::BundleAdjustment (libs/sfm/bundle_adjustment.cc) ---- */
+
+#define MI_DMRECON_BA_CAMERAS 1             /* BundleAdjustment::BAMode (bundle_adjustment.h:54-59) */
+#define MI_DMRECON_BA_POINTS 2
+#define MI_DMRECON_BA_CAMERAS_AND_POINTS 3
+
+/* BundleAdjustment::Options (bundle_adjustment.h:61-74, :139-147) without verbose_output, and
+ * LinearSolver::Options::cg_max_iterations; mi_dmrecon_ba_options_default sets the reference's defaults:
+ * cameras and points, free intrinsics, 50, 0, 1e-4, 1e-8, 1000. */
+typedef struct mi_dmrecon_ba_options {
+    int32_t bundle_mode;
+    int32_t fixed_intrinsics;
+    int32_t lm_max_iterations;
+    int32_t lm_min_iterations;
+    double  lm_delta_threshold;
+    double  lm_mse_threshold;
+    int32_t cg_max_iterations;
+    int32_t reserved;
+} mi_dmrecon_ba_options;
+
+/* sfm::ba::Camera, Point3D and Observation (libs/sfm/ba_types.h:12-36); rotation is row-major, world to camera */
+typedef struct mi_dmrecon_ba_camera {
+    double focal_length;
+    double distortion[2];
+    double translation[3];
+    double rotation[9];
+} mi_dmrecon_ba_camera;
+
+typedef struct mi_dmrecon_ba_point {
+    double  pos[3];
+    int32_t is_constant;
+    int32_t reserved;
+} mi_dmrecon_ba_point;
+
+typedef struct mi_dmrecon_ba_observation {
+    double  pos[2];
+    int32_t camera_id;
+    int32_t point_id;
+} mi_dmrecon_ba_observation;
+
+/* BundleAdjustment::Status (bundle_adjustment.h:76-87) without runtime_ms */
+typedef struct mi_dmrecon_ba_status {
+    double  initial_mse;
+    double  final_mse;
+    int32_t num_lm_iterations;
+    int32_t num_lm_successful_iterations;
+    int32_t num_lm_unsuccessful_iterations;
+    int32_t num_cg_iterations;
+} mi_dmrecon_ba_status;
+
+/* One LM iteration: what the reference's verbose line says of it (bundle_adjustment.cc:142-171) */
+typedef struct mi_dmrecon_ba_trace {
+    double  mse_before;
+    double  mse_after;          /* of the candidate, accepted or not */
+    double  radius;             /* the trust region radius the step was solved with */
+    int32_t cg_iterations;
+    int32_t accepted;
+} mi_dmrecon_ba_trace;
+
+void mi_dmrecon_ba_options_default(mi_dmrecon_ba_options* o);
+
+/* BundleAdjustment::optimize (bundle_adjustment.cc:32-201) on the context's device; cameras and points are read and, on
+ * success, overwritten with the optimised ones.
+ * Residual per observation (:204-284): p = R X + t, (ix, iy) = (p.x, p.y) / p.z, times 1 + r2 (k0 + k1 r2) with
+ * r2 = ix^2 + iy^2, times the focal length, minus the observed position; the MSE is the sum of squares over n_observations.
+ * Jacobian (:381-635): 9 camera parameters (f, k0, k1, t, r) in the full chain-rule form the reference compiles
+ * (:544-632); with fixed_intrinsics 6 (t, r) in the form that treats the distortion factor as constant (:438-465); the
+ * block of a point with is_constant is zero (:334-338).
+ * Linear step (ba_linear_solver.cc:141-243): B = Jc^T Jc per camera, C = Jp^T Jp per point, v = -Jc^T F, w = -Jp^T F; both
+ * diagonals times 1 + 1 / radius; C inverted per 3 x 3 block by determinant and adjugate, a block whose determinant lies
+ * within +-MATH_DBL_EPS of zero left as it is (:75-77: constant points and points nobody observes get a zero step);
+ * preconditioned CG (ba_conjugate_gradient.h:132-210: x0 = 0, converged when r.r < 1e-20 before preconditioning, at most
+ * cg_max_iterations) on S dy = v - E C^-1 w with the Cholesky inverse of each regularised camera block as preconditioner,
+ * entries that are not finite set to 0 (:29-54); dz = C^-1 (w - E^T dy); predicted_error_decrease as in :236-240.  S and E
+ * are never formed (mve_amd/csrc/ba_device.hip).  MI_DMRECON_BA_CAMERAS: the same CG on the regularised B with its
+ * reciprocal diagonal as preconditioner (:245-294); MI_DMRECON_BA_POINTS: d = C^-1 w, no CG iteration (:295-302).
+ * LM loop (bundle_adjustment.cc:73-201): radius 1000 at first; candidates from update_camera / update_point (:662-697, the
+ * Rodrigues matrix of the rotation update from the left, :287-304); a step is accepted if the MSE strictly falls; the radius
+ * is divided by max(1/3, 1 - (2 rho - 1)^3) with rho = delta_mse n_observations / predicted_error_decrease after a success
+ * and halved after a failure; the three termination tests in the reference's order.
+ * trace: optional (NULL with trace_capacity 0); LM iteration i < trace_capacity writes trace[i].
+ * Domain: finite values, every point in front of its cameras, and in a mode that moves cameras every camera has
+ * observations.  NO bit-parity with the reference is claimed, for the reasons given above for RANSAC: the reference is built
+ * with -funsafe-math-optimizations and adds in the order of its sparse matrices, this library in point and camera order;
+ * steps agree to the conditioning of the system, and the iteration counts agree unless a test is passed by less than that.
+ * The same input gives the same bytes on every run and on every fork: no sum depends on scheduling, and none on the
+ * caller's observation order beyond the order of a point's observations among themselves.
+ * MI_DMRECON_EINVAL, naming the offender, before anything is allocated or launched: a null pointer (trace aside); a
+ * trace_capacity that is negative, or positive without trace; a bundle_mode that is not 1, 2 or 3; lm_max_iterations or
+ * cg_max_iterations below 1 (the reference would run one LM iteration, or a CG that never moves, regardless);
+ * a negative lm_min_iterations; n_cameras, n_points or n_observations outside 1 ... 2^27; a focal length that is not
+ * positive; a camera_id or point_id out of range (:44-70).  Outputs are untouched by a failed call.
+ * The buffers belong to the context and grow only.  Contexts forked from one parent (mi_dmrecon_ctx_fork) run their calls
+ * on their own streams, one host thread per context. */
+int mi_dmrecon_ba_optimize(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* options,
+    int32_t n_cameras, mi_dmrecon_ba_camera* cameras,               /* in, out */
+    int32_t n_points, mi_dmrecon_ba_point* points,                  /* in, out */
+    int32_t n_observations, const mi_dmrecon_ba_observation* observations,
+    mi_dmrecon_ba_status* status,
+    mi_dmrecon_ba_trace* trace, int32_t trace_capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ EXPORTS = [
     "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
     "mi_dmrecon_sift_run", "mi_dmrecon_sift_get",
     "mi_dmrecon_surf_run", "mi_dmrecon_surf_get",
+    "mi_dmrecon_ba_options_default", "mi_dmrecon_ba_optimize",
 ]
 
 # the test hooks of include/mi_dmrecon_debug.h (EXPORTS is the drop-in boundary, include/mi_dmrecon.h, alone)
@@ -62,6 +63,8 @@ DEBUG_EXPORTS = [
 MATCH_SIFT, MATCH_SURF = 0, 1      # MI_DMRECON_MATCH_SIFT / _SURF: 128 unsigned dims / 64 signed dims
 MATCH_F32, MATCH_I16 = 0, 1        # MI_DMRECON_MATCH_F32 / _I16
 RANSAC_TILE, RANSAC_CHUNK = 128, 256   # mve_amd/csrc/ransac_device.h: iterations x matches of one workgroup of k_ransac_count
+BA_CAM_BLOCK, BA_POINT_LANES = 256, 4  # mve_amd/csrc/ba_device.h: threads of a camera's workgroup, lanes that share a point
+BA_CAMERAS, BA_POINTS, BA_CAMERAS_AND_POINTS = 1, 2, 3    # MI_DMRECON_BA_*: BundleAdjustment::BAMode
 
 
 class CCamera(ctypes.Structure):
@@ -129,6 +132,29 @@ class CSurfOptions(ctypes.Structure):
 
 SURF_DEFAULTS = dict(contrast_threshold=500.0, use_upright_descriptor=False)            # Surf::Options::Options (surf.h:161-168)
 SURF_KEYPOINT = SIFT_KEYPOINT
+
+
+class CBaOptions(ctypes.Structure):
+    """mi_dmrecon_ba_options = sfm::ba::BundleAdjustment::Options (libs/sfm/bundle_adjustment.h:61-74) and cg_max_iterations."""
+    _fields_ = [("bundle_mode", ctypes.c_int32), ("fixed_intrinsics", ctypes.c_int32), ("lm_max_iterations", ctypes.c_int32),
+                ("lm_min_iterations", ctypes.c_int32), ("lm_delta_threshold", ctypes.c_double), ("lm_mse_threshold", ctypes.c_double),
+                ("cg_max_iterations", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class CBaStatus(ctypes.Structure):
+    """mi_dmrecon_ba_status = BundleAdjustment::Status (bundle_adjustment.h:76-87) without the runtime."""
+    _fields_ = [("initial_mse", ctypes.c_double), ("final_mse", ctypes.c_double), ("num_lm_iterations", ctypes.c_int32),
+                ("num_lm_successful_iterations", ctypes.c_int32), ("num_lm_unsuccessful_iterations", ctypes.c_int32),
+                ("num_cg_iterations", ctypes.c_int32)]
+
+
+BA_DEFAULTS = dict(bundle_mode=BA_CAMERAS_AND_POINTS, fixed_intrinsics=False, lm_max_iterations=50, lm_min_iterations=0,
+                   lm_delta_threshold=1e-4, lm_mse_threshold=1e-8, cg_max_iterations=1000)      # bundle_adjustment.h:139-147, ba_linear_solver.h
+BA_CAMERA = np.dtype([("focal_length", np.float64), ("distortion", np.float64, 2), ("translation", np.float64, 3), ("rotation", np.float64, 9)])
+BA_POINT = np.dtype([("pos", np.float64, 3), ("is_constant", np.int32), ("reserved", np.int32)])
+BA_OBSERVATION = np.dtype([("pos", np.float64, 2), ("camera_id", np.int32), ("point_id", np.int32)])
+BA_TRACE = np.dtype([("mse_before", np.float64), ("mse_after", np.float64), ("radius", np.float64), ("cg_iterations", np.int32),
+                     ("accepted", np.int32)])
 
 
 class CProgress(ctypes.Structure):
@@ -251,6 +277,10 @@ def load_library() -> ctypes.CDLL:
     if hasattr(L, "mi_dmrecon_surf_run"):
         L.mi_dmrecon_surf_run.argtypes = [vp, ctypes.POINTER(CSurfOptions), vp, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.mi_dmrecon_surf_get.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "mi_dmrecon_ba_optimize"):
+        L.mi_dmrecon_ba_options_default.argtypes = [ctypes.POINTER(CBaOptions)]
+        L.mi_dmrecon_ba_options_default.restype = None
+        L.mi_dmrecon_ba_optimize.argtypes = [vp, ctypes.POINTER(CBaOptions), i32, vp, i32, vp, i32, vp, ctypes.POINTER(CBaStatus), vp, i32]
     if hasattr(L, "mi_dmrecon_debug_match_get"):                                                             # test hooks
         ll = ctypes.c_longlong
         L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
@@ -823,6 +853,32 @@ class Context:
         if rc < 0:
             _raise(rc)
         return kp, xyso, desc
+
+    def bundle_adjust(self, cameras, points, observations, **options):
+        """sfm::ba::BundleAdjustment::optimize (libs/sfm/bundle_adjustment.cc) on the GPU (mi_dmrecon_ba_optimize).  ``cameras``,
+        ``points``, ``observations``: record arrays of BA_CAMERA, BA_POINT and BA_OBSERVATION; ``options``: the fields of
+        BA_DEFAULTS.  Returns (cameras, points, status, trace): optimised copies, the fields of BundleAdjustment::Status as a
+        dict, and one BA_TRACE record per LM iteration.  The inputs are not modified."""
+        if not hasattr(self._L, "mi_dmrecon_ba_optimize"):
+            raise RuntimeError("%s has no mi_dmrecon_ba_optimize: rebuild the library" % LIB_PATH)
+        unknown = set(options) - set(BA_DEFAULTS)
+        if unknown:
+            raise TypeError("bundle_adjust: unknown options %s" % sorted(unknown))
+        cams = np.array(cameras, dtype=BA_CAMERA, ndmin=1)         # copies: the call writes into them
+        pts = np.array(points, dtype=BA_POINT, ndmin=1)
+        obs = np.ascontiguousarray(observations, dtype=BA_OBSERVATION)
+        o = dict(BA_DEFAULTS, **options)
+        opt = CBaOptions(int(o["bundle_mode"]), int(bool(o["fixed_intrinsics"])), int(o["lm_max_iterations"]), int(o["lm_min_iterations"]),
+                         float(o["lm_delta_threshold"]), float(o["lm_mse_threshold"]), int(o["cg_max_iterations"]), 0)
+        capacity = max(int(o["lm_max_iterations"]), int(o["lm_min_iterations"]), 0)
+        trace = np.zeros(capacity, BA_TRACE)
+        status = CBaStatus()
+        rc = self._L.mi_dmrecon_ba_optimize(self._h, ctypes.byref(opt), len(cams), _ptr(cams), len(pts), _ptr(pts), len(obs), _ptr(obs),
+                                            ctypes.byref(status), _ptr(trace) if capacity else None, capacity)
+        if rc < 0:
+            _raise(rc)
+        st = {f: getattr(status, f) for f, _ in CBaStatus._fields_}
+        return cams, pts, st, trace[:st["num_lm_iterations"]]
 
     @property
     def ransac_sweep_capped(self) -> int:

@@ -467,6 +467,7 @@ struct SceneStore {
 void mi_ransac_release(struct RansacState* s);   /* ransac_host.cpp */
 void mi_sift_release(struct SiftState* s);       /* sift_host.cpp */
 void mi_surf_release(struct SurfState* s);       /* surf_host.cpp */
+void mi_ba_release(struct BaState* s);           /* ba_host.cpp */
 
 struct mi_dmrecon_ctx {
     int device = 0;
@@ -486,6 +487,7 @@ struct mi_dmrecon_ctx {
     struct RansacState* ransac = nullptr;    /* buffers of mi_dmrecon_ransac_fundamental (ransac_host.cpp), made by its first call */
     struct SiftState* sift = nullptr;        /* buffers and last results of mi_dmrecon_sift_run (sift_host.cpp), likewise */
     struct SurfState* surf = nullptr;        /* ... and of mi_dmrecon_surf_run (surf_host.cpp) */
+    struct BaState* ba = nullptr;            /* ... and of mi_dmrecon_ba_optimize (ba_host.cpp) */
 };
 
 namespace {
@@ -1499,6 +1501,7 @@ void mi_dmrecon_ctx_destroy(mi_dmrecon_ctx* c) {
     mi_ransac_release(c->ransac);
     mi_sift_release(c->sift);
     mi_surf_release(c->surf);
+    mi_ba_release(c->ba);
     if (c->d_counters) (void)hipFree(c->d_counters);
     (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -3603,3 +3606,4 @@ int mi_host_ctx_device(const mi_dmrecon_ctx* c) { return c ? c->device : -1; }
 RansacState** mi_host_ctx_ransac(mi_dmrecon_ctx* c) { return &c->ransac; }
 SiftState** mi_host_ctx_sift(mi_dmrecon_ctx* c) { return &c->sift; }
 SurfState** mi_host_ctx_surf(mi_dmrecon_ctx* c) { return &c->surf; }
+BaState** mi_host_ctx_ba(mi_dmrecon_ctx* c) { return &c->ba; }
