@@ -471,8 +471,65 @@ int mi_dmrecon_ransac_fundamental(mi_dmrecon_ctx* ctx, int32_t n_jobs, const mi_
     int32_t* const* iteration_counts,   /* optional (NULL, or NULL per job): n_iterations inlier counts */
     double*  const* iteration_F);       /* optional likewise: n_iterations x 9 */
 
-/* Solves (of the 8 x 9 system or of the 3 x 3 rank step) of this context's calls so far that were still rotating after
- * the last Jacobi sweep the kernel allows (30); their hypotheses were kept as they stood.  0 is the expected value. */
+/* ---- ... RANSAC for the homography of a pair (bundler::InitialPair) and for the pose of a new view (bundler::Incremental) -- */
+
+/* n_jobs sfm::RansacHomography::estimate (libs/sfm/ransac_homography.cc:27-98) in three launches; a job is a
+ * mi_dmrecon_ransac_job whose samples are n_iterations x 4 and whose n_matches is >= 4.  Per iteration: homography_dlt of its
+ * four sampled matches (libs/sfm/homography.cc:20-63: the right singular vector of the 8 x 9 system for its smallest singular
+ * value), divided by its last element (ransac_homography.cc:82), and the number of matches with
+ * symmetric_transfer_error(H, m) < threshold^2 (homography.cc:65-88).  H^-1 is computed once per iteration, by adjugate over
+ * determinant; the reference inverts once per match.  Winner, outputs, the optional per-iteration outputs (iteration_H[j]:
+ * n_iterations x 9), errors, limits, buffers and forks: as for mi_dmrecon_ransac_fundamental, with 4 in the place of 8.
+ * A hypothesis whose H or H^-1 is not finite has count 0.  NO bit-parity with the reference is claimed, for the reasons given
+ * there: H agrees to the conditioning of the sample, the inlier sets except for matches whose error lies within rounding of
+ * the threshold.  The inlier test is written without a division (both sides times the squares of the two third coordinates);
+ * a zero third coordinate is "not an inlier" in both forms. */
+int mi_dmrecon_ransac_homography(mi_dmrecon_ctx* ctx, int32_t n_jobs, const mi_dmrecon_ransac_job* jobs,
+    int32_t* best_iteration,        /* per job; -1: nothing beat inliers_to_beat, the job's other outputs untouched */
+    double*  homography,            /* 9 per job, row-major, the winning hypothesis as computed */
+    int32_t* n_inliers,             /* per job */
+    int32_t* const* inliers,        /* per job: room for n_matches indices, written ascending */
+    int32_t* const* iteration_counts,   /* optional (NULL, or NULL per job): n_iterations inlier counts */
+    double*  const* iteration_H);       /* optional likewise: n_iterations x 9 */
+
+/* One sfm::RansacPoseP3P::estimate (libs/sfm/ransac_pose_p3p.cc:26-78) with its random draws made by the caller. */
+typedef struct mi_dmrecon_ransac_p3p_job {
+    int32_t n_corr;             /* >= 3 */
+    int32_t n_iterations;       /* >= 1 */
+    const double*  corr;        /* n_corr x 5: p3d.x p3d.y p3d.z p2d.x p2d.y (sfm::Correspondence2D3D) */
+    double  k_matrix[9];        /* the calibration, row-major; it must have an inverse */
+    const int32_t* samples;     /* n_iterations x 3 indices into corr, ascending and distinct within a row */
+    double  threshold;          /* RansacPoseP3P::Options::threshold; compared squared */
+    int32_t inliers_to_beat;    /* result->inliers.size() on entry; a hypothesis wins only with MORE */
+} mi_dmrecon_ransac_p3p_job;
+
+/* n_jobs estimates in three launches.  Per iteration: pose_p3p_kneip (libs/sfm/pose_p3p.cc:74-236) of its three sampled
+ * correspondences, with directions K^-1 (u, v, 1), which gives FOUR hypotheses, one per root of the quartic in the reference's
+ * order (:63-66); hypothesis 4 * iteration + root is the pose [R|t], counted by the correspondences with
+ * |(K [R|t] (X, 1)).xy / .z - uv|^2 < threshold^2 (find_inliers, ransac_pose_p3p.cc:106-122; no test on the sign of .z).
+ * A collinear sample (pose_p3p.cc:80-85: no solution) gives four hypotheses of NaN, a root outside [-1, 1] a pose of NaN as in
+ * the reference; both count 0.  The winner of a job is the FIRST hypothesis whose count is strictly greater than every count
+ * before it and greater than inliers_to_beat: the order of the reference's loop in one thread (its OpenMP loop makes the
+ * winner among equal counts depend on the schedule).
+ * Outputs: best_hypothesis [n_jobs] (-1: none, the job's other outputs untouched); pose [12 n_jobs], row-major 3 x 4;
+ * n_inliers; inliers[j]: room for n_corr indices, ascending.  Optional: hypothesis_counts[j], 4 n_iterations counts, and
+ * hypothesis_pose[j], 4 n_iterations x 12.
+ * All arithmetic is double; the complex steps of the quartic are written in real pairs (principal square and cube roots).
+ * NO bit-parity with the reference is claimed: poses agree to the conditioning of the quartic (a nearly double root moves
+ * with rounding), the inlier sets except for correspondences whose error lies within rounding of the threshold.
+ * Errors, limits (counted in hypotheses), buffers and forks: as for mi_dmrecon_ransac_fundamental, with 3 in the place of 8,
+ * and MI_DMRECON_EINVAL for a k_matrix without a finite inverse. */
+int mi_dmrecon_ransac_pose_three_point(mi_dmrecon_ctx* ctx, int32_t n_jobs, const mi_dmrecon_ransac_p3p_job* jobs,
+    int32_t* best_hypothesis,       /* per job: 4 * iteration + root; -1: none */
+    double*  pose,                  /* 12 per job, row-major 3 x 4 */
+    int32_t* n_inliers,             /* per job */
+    int32_t* const* inliers,        /* per job: room for n_corr indices, written ascending */
+    int32_t* const* hypothesis_counts,  /* optional (NULL, or NULL per job): 4 n_iterations inlier counts */
+    double*  const* hypothesis_pose);   /* optional likewise: 4 n_iterations x 12 */
+
+/* Jacobi solves (of the 8 x 9 system of F or H, or of the 3 x 3 rank step of F) of this context's calls so far that were
+ * still rotating after the last sweep the kernel allows (30); their hypotheses were kept as they stood.  0 is the expected
+ * value. */
 long long mi_dmrecon_ransac_sweep_capped(mi_dmrecon_ctx* ctx);
 
 /* ---- ... and where its descriptors come from: sfm::Sift (libs/sfm/sift.cc), detection and description of one image ---- */

@@ -48,6 +48,7 @@ EXPORTS = [
     "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
     "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
+    "mi_dmrecon_ransac_homography", "mi_dmrecon_ransac_pose_three_point",
     "mi_dmrecon_sift_run", "mi_dmrecon_sift_get",
     "mi_dmrecon_surf_run", "mi_dmrecon_surf_get",
     "mi_dmrecon_ba_options_default", "mi_dmrecon_ba_optimize",
@@ -111,6 +112,12 @@ class CMatchJob(ctypes.Structure):
 class CRansacJob(ctypes.Structure):
     _fields_ = [("n_matches", ctypes.c_int32), ("n_iterations", ctypes.c_int32), ("matches", ctypes.c_void_p),
                 ("samples", ctypes.c_void_p), ("threshold", ctypes.c_double), ("inliers_to_beat", ctypes.c_int32)]
+
+
+class CRansacP3PJob(ctypes.Structure):
+    _fields_ = [("n_corr", ctypes.c_int32), ("n_iterations", ctypes.c_int32), ("corr", ctypes.c_void_p),
+                ("k_matrix", ctypes.c_double * 9), ("samples", ctypes.c_void_p), ("threshold", ctypes.c_double),
+                ("inliers_to_beat", ctypes.c_int32)]
 
 
 class CSiftOptions(ctypes.Structure):
@@ -271,6 +278,9 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_ransac_fundamental.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.mi_dmrecon_ransac_sweep_capped.argtypes = [vp]
         L.mi_dmrecon_ransac_sweep_capped.restype = ctypes.c_longlong
+    for name in ("mi_dmrecon_ransac_homography", "mi_dmrecon_ransac_pose_three_point"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "mi_dmrecon_sift_run"):
         L.mi_dmrecon_sift_run.argtypes = [vp, ctypes.POINTER(CSiftOptions), vp, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
         L.mi_dmrecon_sift_get.argtypes = [vp, vp, vp, vp]
@@ -791,6 +801,81 @@ class Context:
             res.append(r)
         return res
 
+    def _ransac(self, symbol, cj, lengths, hyps, shape, out, per_iteration):
+        """The call that ransac_homography and ransac_pose_p3p share: ``lengths`` list entries and ``hyps`` hypotheses per
+        job, a winner of ``shape``.  Returns best, the (model, inliers) pairs written into, n_inliers, counts, all."""
+        if not hasattr(self._L, symbol):
+            raise RuntimeError("%s has no %s: rebuild the library" % (LIB_PATH, symbol))
+        n, size = len(lengths), int(np.prod(shape))
+        if out is None:
+            out = [(np.full(shape, np.nan), np.full(m, -1, np.int32)) for m in lengths]
+        for (M, inl), m in zip(out, lengths):
+            if M.dtype != np.float64 or M.size != size or inl.dtype != np.int32 or inl.size < m \
+                    or not M.flags.c_contiguous or not inl.flags.c_contiguous:
+                raise ValueError("out: per job a contiguous %s float64 and an int32 array with room for every list entry" % (shape,))
+        best, n_inl = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+        model = np.stack([o[0].ravel() for o in out])
+        p_inl = (ctypes.c_void_p * n)(*[o[1].ctypes.data for o in out])
+        counts = [np.zeros(h, np.int32) for h in hyps] if per_iteration else None
+        every = [np.zeros((h, size)) for h in hyps] if per_iteration else None
+        p_counts = (ctypes.c_void_p * n)(*[a.ctypes.data for a in counts]) if per_iteration else None
+        p_every = (ctypes.c_void_p * n)(*[a.ctypes.data for a in every]) if per_iteration else None
+        rc = getattr(self._L, symbol)(self._h, n, ctypes.cast(cj, ctypes.c_void_p), _ptr(best), _ptr(model), _ptr(n_inl),
+                                      ctypes.cast(p_inl, ctypes.c_void_p),
+                                      ctypes.cast(p_counts, ctypes.c_void_p) if per_iteration else None,
+                                      ctypes.cast(p_every, ctypes.c_void_p) if per_iteration else None)
+        if rc < 0:
+            _raise(rc)
+        for k in range(n):
+            out[k][0][...] = model[k].reshape(out[k][0].shape)
+        return best, out, n_inl, counts, every
+
+    def ransac_homography(self, jobs, per_iteration: bool = False, out=None):
+        """sfm::RansacHomography::estimate (libs/sfm/ransac_homography.cc:27-98) for a list of jobs in one call
+        (mi_dmrecon_ransac_homography).  A job is as for ransac_fundamental, with samples (it, 4).  Returns per job a dict
+        of ``best_iteration`` (-1: none), ``H`` (3, 3) and ``inliers`` (int32, ascending), with ``per_iteration`` also
+        ``counts`` (it,) and ``H_all`` (it, 3, 3).  ``out``: per job the caller's own (H (3, 3) float64, inliers (n,) int32);
+        a job without a winner leaves them as they were (without ``out``: NaN and empty)."""
+        if len(jobs) == 0:
+            return []
+        ms = [np.ascontiguousarray(j[0], np.float64).reshape(-1, 4) for j in jobs]
+        ss = [np.ascontiguousarray(j[1], np.int32).reshape(-1, 4) for j in jobs]
+        cj = (CRansacJob * len(jobs))(*[CRansacJob(len(m), len(s), m.ctypes.data, s.ctypes.data, float(j[2]), int(j[3]) if len(j) > 3 else 0)
+                                        for j, m, s in zip(jobs, ms, ss)])
+        best, out, n_inl, counts, every = self._ransac("mi_dmrecon_ransac_homography", cj, [len(m) for m in ms], [len(s) for s in ss],
+                                                       (3, 3), out, per_iteration)
+        res = []
+        for k in range(len(jobs)):
+            r = dict(best_iteration=int(best[k]), H=out[k][0], inliers=out[k][1][:n_inl[k]])
+            if per_iteration:
+                r["counts"], r["H_all"] = counts[k], every[k].reshape(-1, 3, 3)
+            res.append(r)
+        return res
+
+    def ransac_pose_p3p(self, jobs, per_iteration: bool = False, out=None):
+        """sfm::RansacPoseP3P::estimate (libs/sfm/ransac_pose_p3p.cc:26-78, in the order of one thread) for a list of jobs in
+        one call (mi_dmrecon_ransac_pose_three_point).  A job is (corr (n, 5) float64 rows X Y Z u v, K (3, 3), samples (it, 3) int32
+        rows of ascending distinct indices, threshold[, inliers_to_beat = 0]).  Returns per job a dict of ``best_hypothesis``
+        (4 * iteration + root; -1: none), ``pose`` (3, 4) and ``inliers``, with ``per_iteration`` also ``counts`` (it, 4) and
+        ``pose_all`` (it, 4, 3, 4), NaN where Kneip's solve has no pose.  ``out``: per job the caller's own (pose (3, 4)
+        float64, inliers (n,) int32), left as they were by a job without a winner."""
+        if len(jobs) == 0:
+            return []
+        cs = [np.ascontiguousarray(j[0], np.float64).reshape(-1, 5) for j in jobs]
+        ss = [np.ascontiguousarray(j[2], np.int32).reshape(-1, 3) for j in jobs]
+        cj = (CRansacP3PJob * len(jobs))(*[
+            CRansacP3PJob(len(c), len(s), c.ctypes.data, (ctypes.c_double * 9)(*np.asarray(j[1], np.float64).reshape(9)), s.ctypes.data,
+                          float(j[3]), int(j[4]) if len(j) > 4 else 0) for j, c, s in zip(jobs, cs, ss)])
+        best, out, n_inl, counts, every = self._ransac("mi_dmrecon_ransac_pose_three_point", cj, [len(c) for c in cs], [4 * len(s) for s in ss],
+                                                       (3, 4), out, per_iteration)
+        res = []
+        for k in range(len(jobs)):
+            r = dict(best_hypothesis=int(best[k]), pose=out[k][0], inliers=out[k][1][:n_inl[k]])
+            if per_iteration:
+                r["counts"], r["pose_all"] = counts[k].reshape(-1, 4), every[k].reshape(-1, 4, 3, 4)
+            res.append(r)
+        return res
+
     def sift(self, image, **options):
         """sfm::Sift::set_image / set_float_image + process (libs/sfm/sift.cc) for one image on the GPU (mi_dmrecon_sift_run,
         mi_dmrecon_sift_get).  ``image``: uint8 or float32, H x W or H x W x 3.  ``options``: the fields of Sift::Options
@@ -882,7 +967,7 @@ class Context:
 
     @property
     def ransac_sweep_capped(self) -> int:
-        """Jacobi solves of this context's ransac_fundamental calls so far that were cut off at the kernel's last sweep."""
+        """Jacobi solves of this context's ransac_fundamental and ransac_homography calls so far that were cut off at the kernel's last sweep."""
         return int(self._L.mi_dmrecon_ransac_sweep_capped(self._h))
 
 

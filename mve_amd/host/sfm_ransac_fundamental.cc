@@ -17,84 +17,19 @@
  * F and the inlier set agree with the reference's to rounding, not bit for bit (include/mi_dmrecon.h).
  *
  * One context for the process, made by the first call on the first entry of MI_DMRECON_DEVICES (default 0), as the other
- * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit.
+ * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit
+ * (ransac_shim.h, shared with the homography and P3P drop-ins).
  */
 #include <cstdint>
-#include <cstdlib>
 #include <iostream>
-#include <mutex>
-#include <set>
-#include <sstream>
 #include <stdexcept>
-#include <string>
 #include <vector>
 
-#include "util/system.h"
 #include "sfm/ransac_fundamental.h"
 
-#include "mi_dmrecon.h"
+#include "ransac_shim.h"
 
 SFM_NAMESPACE_BEGIN
-
-namespace {
-
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("sfm::RansacFundamental (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
-
-/* the process-wide context and its forks */
-struct Contexts
-{
-    std::mutex mutex;
-    mi_dmrecon_ctx* parent = nullptr;
-    std::vector<mi_dmrecon_ctx*> forks;
-    ~Contexts (void)
-    {
-        for (std::size_t i = 0; i < this->forks.size(); ++i)
-            mi_dmrecon_ctx_destroy(this->forks[i]);
-        if (this->parent != nullptr)
-            mi_dmrecon_ctx_destroy(this->parent);
-    }
-};
-
-Contexts contexts;
-
-mi_dmrecon_ctx* context_of_this_thread(void)
-{
-    static thread_local mi_dmrecon_ctx* mine = nullptr;
-    if (mine != nullptr)
-        return mine;
-    std::lock_guard<std::mutex> lock(contexts.mutex);
-    if (contexts.parent == nullptr)
-        check(mi_dmrecon_ctx_create(first_device(), &contexts.parent), "mi_dmrecon_ctx_create");
-    check(mi_dmrecon_ctx_fork(contexts.parent, &mine), "mi_dmrecon_ctx_fork");
-    contexts.forks.push_back(mine);
-    return mine;
-}
-
-}  /* namespace */
 
 RansacFundamental::RansacFundamental (Options const& options)
     : opts(options)
@@ -117,15 +52,7 @@ RansacFundamental::estimate (Correspondences2D2D const& matches, Result* result)
 
     static_assert(sizeof(Correspondence2D2D) == 4 * sizeof(double), "a match is p1.x p1.y p2.x p2.y");
     static_assert(sizeof(int) == sizeof(int32_t), "Result::inliers holds int");
-    std::vector<int32_t> samples;
-    samples.reserve(static_cast<std::size_t>(this->opts.max_iterations) * 8);
-    for (int iteration = 0; iteration < this->opts.max_iterations; ++iteration)
-    {
-        std::set<int> drawn;
-        while (drawn.size() < 8)
-            drawn.insert(util::system::rand_int() % matches.size());
-        samples.insert(samples.end(), drawn.begin(), drawn.end());
-    }
+    std::vector<int32_t> const samples = mi_ransac_shim::draw_samples(this->opts.max_iterations, 8, matches.size());
 
     mi_dmrecon_ransac_job job;
     job.n_matches = static_cast<int32_t>(matches.size());
@@ -141,7 +68,7 @@ RansacFundamental::estimate (Correspondences2D2D const& matches, Result* result)
     std::vector<int32_t> counts(this->opts.verbose_output ? this->opts.max_iterations : 0);
     int32_t* inliers_ptr = inliers.data();
     int32_t* counts_ptr = counts.data();
-    check(mi_dmrecon_ransac_fundamental(context_of_this_thread(), 1, &job, &best_iteration, fundamental, &n_inliers,
+    mi_ransac_shim::check(mi_dmrecon_ransac_fundamental(mi_ransac_shim::context_of_this_thread("sfm::RansacFundamental"), 1, &job, &best_iteration, fundamental, &n_inliers,
         &inliers_ptr, this->opts.verbose_output ? &counts_ptr : nullptr, nullptr), "mi_dmrecon_ransac_fundamental");
 
     if (this->opts.verbose_output)
