@@ -430,6 +430,27 @@ def _raise(rc: int):
     raise RuntimeError(msg)                   # std::runtime_error
 
 
+def _need(L, symbol: str, named: str = None):
+    """A library older than this file (or a stand-in of the tests) may lack an entry point: say so instead of AttributeError."""
+    if not hasattr(L, symbol):
+        raise RuntimeError("%s has no %s: rebuild the library" % (LIB_PATH, named or symbol))
+
+
+def _feature_input(who: str, image, dtypes, defaults, options):
+    """What Context.sift and Context.surf share: the image checked and contiguous, its size, the options over their defaults."""
+    unknown = set(options) - set(defaults)
+    if unknown:
+        raise TypeError("%s: unknown options %s" % (who, sorted(unknown)))
+    img = np.asarray(image)
+    if img.dtype not in dtypes:
+        raise ValueError("%s: image must be %s, not %s" % (who, " or ".join(np.dtype(t).name for t in dtypes), img.dtype))
+    if img.ndim not in (2, 3):
+        raise ValueError("%s: image must be H x W or H x W x channels" % who)
+    img = np.ascontiguousarray(img)
+    h, w = img.shape[:2]
+    return img, w, h, img.shape[2] if img.ndim == 3 else 1, dict(defaults, **options)
+
+
 @dataclass
 class Settings:
     """mvs::Settings (libs/dmrecon/settings.h:22-52), same names and defaults."""
@@ -762,50 +783,26 @@ class Context:
         ascending), with ``per_iteration`` also ``counts`` (it,) and ``F_all`` (it, 3, 3).
         ``out``: per job the caller's own (F (3, 3) float64, inliers (n,) int32) to write into, as the reference writes
         into the Result it is given: a job without a winner leaves them as they were (without ``out``: NaN and empty)."""
-        if not hasattr(self._L, "mi_dmrecon_ransac_fundamental"):
-            raise RuntimeError("%s has no mi_dmrecon_ransac_fundamental: rebuild the library" % LIB_PATH)
-        n = len(jobs)
-        if n == 0:
+        if len(jobs) == 0:
             return []
         ms = [np.ascontiguousarray(j[0], np.float64).reshape(-1, 4) for j in jobs]
         ss = [np.ascontiguousarray(j[1], np.int32).reshape(-1, 8) for j in jobs]
-        cj = (CRansacJob * n)(*[CRansacJob(len(m), len(s), m.ctypes.data, s.ctypes.data, float(j[2]), int(j[3]) if len(j) > 3 else 0)
-                                for j, m, s in zip(jobs, ms, ss)])
-        if out is None:
-            out = [(np.full((3, 3), np.nan), np.full(len(m), -1, np.int32)) for m in ms]
-        for (F, inl), m in zip(out, ms):
-            if F.dtype != np.float64 or F.size != 9 or inl.dtype != np.int32 or inl.size < len(m) \
-                    or not F.flags.c_contiguous or not inl.flags.c_contiguous:
-                raise ValueError("out: per job a contiguous (3, 3) float64 and an int32 array with room for every match")
-        best, n_inl = np.full(n, -1, np.int32), np.zeros(n, np.int32)
-        F = np.zeros((n, 9))
-        for k, (Fk, _) in enumerate(out):
-            F[k] = Fk.ravel()
-        p_inl = (ctypes.c_void_p * n)(*[o[1].ctypes.data for o in out])
-        counts = [np.zeros(len(s), np.int32) for s in ss] if per_iteration else None
-        F_all = [np.zeros((len(s), 3, 3)) for s in ss] if per_iteration else None
-        p_counts = (ctypes.c_void_p * n)(*[a.ctypes.data for a in counts]) if per_iteration else None
-        p_F = (ctypes.c_void_p * n)(*[a.ctypes.data for a in F_all]) if per_iteration else None
-        rc = self._L.mi_dmrecon_ransac_fundamental(self._h, n, ctypes.cast(cj, ctypes.c_void_p), _ptr(best), _ptr(F), _ptr(n_inl),
-                                                   ctypes.cast(p_inl, ctypes.c_void_p),
-                                                   ctypes.cast(p_counts, ctypes.c_void_p) if per_iteration else None,
-                                                   ctypes.cast(p_F, ctypes.c_void_p) if per_iteration else None)
-        if rc < 0:
-            _raise(rc)
+        cj = (CRansacJob * len(jobs))(*[CRansacJob(len(m), len(s), m.ctypes.data, s.ctypes.data, float(j[2]), int(j[3]) if len(j) > 3 else 0)
+                                        for j, m, s in zip(jobs, ms, ss)])
+        best, out, n_inl, counts, every = self._ransac("mi_dmrecon_ransac_fundamental", cj, [len(m) for m in ms], [len(s) for s in ss],
+                                                       (3, 3), out, per_iteration)
         res = []
-        for k in range(n):
-            out[k][0][...] = F[k].reshape(out[k][0].shape)
+        for k in range(len(jobs)):
             r = dict(best_iteration=int(best[k]), F=out[k][0], inliers=out[k][1][:n_inl[k]])
             if per_iteration:
-                r["counts"], r["F_all"] = counts[k], F_all[k]
+                r["counts"], r["F_all"] = counts[k], every[k].reshape(-1, 3, 3)
             res.append(r)
         return res
 
     def _ransac(self, symbol, cj, lengths, hyps, shape, out, per_iteration):
-        """The call that ransac_homography and ransac_pose_p3p share: ``lengths`` list entries and ``hyps`` hypotheses per
+        """The call that the three ransac_* methods share: ``lengths`` list entries and ``hyps`` hypotheses per
         job, a winner of ``shape``.  Returns best, the (model, inliers) pairs written into, n_inliers, counts, all."""
-        if not hasattr(self._L, symbol):
-            raise RuntimeError("%s has no %s: rebuild the library" % (LIB_PATH, symbol))
+        _need(self._L, symbol)
         n, size = len(lengths), int(np.prod(shape))
         if out is None:
             out = [(np.full(shape, np.nan), np.full(m, -1, np.int32)) for m in lengths]
@@ -881,20 +878,8 @@ class Context:
         mi_dmrecon_sift_get).  ``image``: uint8 or float32, H x W or H x W x 3.  ``options``: the fields of Sift::Options
         (SIFT_DEFAULTS).  Returns (keypoints, xyso, descriptors): a SIFT_KEYPOINT record array in the reference's order, and
         per descriptor x, y, scale, orientation (n, 4) and the 128 values (n, 128), float32."""
-        if not hasattr(self._L, "mi_dmrecon_sift_run"):
-            raise RuntimeError("%s has no mi_dmrecon_sift_run: rebuild the library" % LIB_PATH)
-        unknown = set(options) - set(SIFT_DEFAULTS)
-        if unknown:
-            raise TypeError("sift: unknown options %s" % sorted(unknown))
-        img = np.asarray(image)
-        if img.dtype not in (np.uint8, np.float32):
-            raise ValueError("sift: image must be uint8 or float32, not %s" % img.dtype)
-        if img.ndim not in (2, 3):
-            raise ValueError("sift: image must be H x W or H x W x channels")
-        img = np.ascontiguousarray(img)
-        h, w = img.shape[:2]
-        channels = img.shape[2] if img.ndim == 3 else 1
-        o = dict(SIFT_DEFAULTS, **options)
+        _need(self._L, "mi_dmrecon_sift_run")
+        img, w, h, channels, o = _feature_input("sift", image, (np.uint8, np.float32), SIFT_DEFAULTS, options)
         opt = CSiftOptions(*[o[f] for f, _ in CSiftOptions._fields_])
         n_kp, n_desc = ctypes.c_int32(0), ctypes.c_int32(0)
         rc = self._L.mi_dmrecon_sift_run(self._h, ctypes.byref(opt), _ptr(img), int(img.dtype == np.float32), w, h, channels,
@@ -913,20 +898,8 @@ class Context:
         ``image``: uint8, H x W or H x W x 3.  ``options``: the fields of Surf::Options (SURF_DEFAULTS).  Returns (keypoints,
         xyso, descriptors): a SURF_KEYPOINT record array in the reference's order, and per descriptor x, y, scale, orientation
         (n, 4) and the 64 values (n, 64), float32."""
-        if not hasattr(self._L, "mi_dmrecon_surf_run"):
-            raise RuntimeError("%s has no mi_dmrecon_surf_run: rebuild the library" % LIB_PATH)
-        unknown = set(options) - set(SURF_DEFAULTS)
-        if unknown:
-            raise TypeError("surf: unknown options %s" % sorted(unknown))
-        img = np.asarray(image)
-        if img.dtype != np.uint8:
-            raise ValueError("surf: image must be uint8, not %s" % img.dtype)
-        if img.ndim not in (2, 3):
-            raise ValueError("surf: image must be H x W or H x W x channels")
-        img = np.ascontiguousarray(img)
-        h, w = img.shape[:2]
-        channels = img.shape[2] if img.ndim == 3 else 1
-        o = dict(SURF_DEFAULTS, **options)
+        _need(self._L, "mi_dmrecon_surf_run")
+        img, w, h, channels, o = _feature_input("surf", image, (np.uint8,), SURF_DEFAULTS, options)
         opt = CSurfOptions(float(o["contrast_threshold"]), int(bool(o["use_upright_descriptor"])))
         n_kp, n_desc = ctypes.c_int32(0), ctypes.c_int32(0)
         rc = self._L.mi_dmrecon_surf_run(self._h, ctypes.byref(opt), _ptr(img), w, h, channels, ctypes.byref(n_kp), ctypes.byref(n_desc))
@@ -944,8 +917,7 @@ class Context:
         ``points``, ``observations``: record arrays of BA_CAMERA, BA_POINT and BA_OBSERVATION; ``options``: the fields of
         BA_DEFAULTS.  Returns (cameras, points, status, trace): optimised copies, the fields of BundleAdjustment::Status as a
         dict, and one BA_TRACE record per LM iteration.  The inputs are not modified."""
-        if not hasattr(self._L, "mi_dmrecon_ba_optimize"):
-            raise RuntimeError("%s has no mi_dmrecon_ba_optimize: rebuild the library" % LIB_PATH)
+        _need(self._L, "mi_dmrecon_ba_optimize")
         unknown = set(options) - set(BA_DEFAULTS)
         if unknown:
             raise TypeError("bundle_adjust: unknown options %s" % sorted(unknown))
@@ -979,8 +951,7 @@ class Matcher:
         self._L = ctx._L
         self._ctx = ctx                 # the handle lives on the context's device
         self._h = None
-        if not hasattr(self._L, "mi_dmrecon_match_create"):
-            raise RuntimeError("%s has no mi_dmrecon_match_* entry points: rebuild the library" % LIB_PATH)
+        _need(self._L, "mi_dmrecon_match_create", "mi_dmrecon_match_* entry points")
         h = ctypes.c_void_p()
         rc = self._L.mi_dmrecon_match_create(ctx._h, int(n_sets), ctypes.byref(h))
         if rc < 0:
@@ -1065,8 +1036,7 @@ class FssrSampler:
         self._L = ctx._L
         self._ctx = ctx                 # the handle uses the context's device and stream
         self._h = None
-        if not hasattr(self._L, "mi_dmrecon_fssr_create"):
-            raise RuntimeError("%s has no mi_dmrecon_fssr_* entry points: rebuild the library" % LIB_PATH)
+        _need(self._L, "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_* entry points")
         samples = np.ascontiguousarray(samples, np.float32)
         if samples.ndim != 2 or samples.shape[1] != 11:
             raise ValueError("samples: (S, 11) float32 expected")

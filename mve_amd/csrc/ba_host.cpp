@@ -14,62 +14,30 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/mi_dmrecon.h"
+#include "host_common.h"
 #include "ba_device.h"
-
-/* dmrecon_host.cpp (not exported, exports.map): the thread-local error message, and the context's device and BA state */
-struct BaState;
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
-BaState** mi_host_ctx_ba(mi_dmrecon_ctx* c);
 
 /* CG iterations enqueued between two reads of the `done` flag (profiles/ba.md; a build with -DBA_CG_BATCH=n measures another) */
 #ifndef BA_CG_BATCH
 #define BA_CG_BATCH 16
 #endif
 
-/* The buffers of a context's calls; they grow only and go with the context (mi_ba_release). */
-struct BaState {
-    size_t cap = 0, h_cap = 0;
-    uint8_t* d_mem = nullptr;                /* lists | two parameter sets | the work arrays of BaWork */
-    uint8_t* h_mem = nullptr;                /* pinned: the lists and the parameters as uploaded and downloaded */
-    BaScalars* d_sc = nullptr;
-    BaScalars* h_sc = nullptr;               /* pinned */
-};
-
-void mi_ba_release(BaState* s) {
-    if (!s) return;
-    if (s->d_mem) (void)hipFree(s->d_mem);
-    if (s->h_mem) (void)hipHostFree(s->h_mem);
-    if (s->d_sc) (void)hipFree(s->d_sc);
-    if (s->h_sc) (void)hipHostFree(s->h_sc);
-    delete s;
-}
-
 namespace {
 
+/* The buffers of a context's calls; they grow only and go with the context. */
+struct BaState : HostModule {
+    Buf d_mem;                               /* lists | two parameter sets | the work arrays of BaWork */
+    PinnedBuf h_mem;                         /* the lists and the parameters as uploaded and downloaded */
+    Buf d_sc;                                /* one BaScalars */
+    PinnedBuf h_sc;
+};
+
 #define BA_MAX_ITEMS (1ll << 27)             /* observations / points / cameras of a call: BA_POINT_LANES * n_points and every slot stay inside int32 */
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), fmt, a, b);
-    return mi_host_fail(code, buf);
-}
-
-#define BA_HIP(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
 
 /* hands out 256-byte aligned pieces of one allocation */
 struct Arena {
     size_t used = 0;
-    size_t take(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
+    size_t take(size_t bytes) { const size_t at = used; used += align256(bytes); return at; }
 };
 
 int validate(const mi_dmrecon_ba_options* o, int32_t nc, const mi_dmrecon_ba_camera* cams, int32_t np, const mi_dmrecon_ba_point* pts,
@@ -121,35 +89,26 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
     for (size_t& at : o_vec) at = A.take(ncam * D * 8);
     const size_t o_cam_part = A.take(ncam * 8), o_blk = A.take(((n + BA_CAM_BLOCK - 1) / BA_CAM_BLOCK) * 8);
 
-    BA_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
-    BaState*& state = *mi_host_ctx_ba(ctx);
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    HostModule*& state = mi_host_ctx_module(ctx, MI_MODULE_BA);
     if (!state) state = new BaState();
-    BaState& s = *state;
-    if (!s.d_sc) {
-        BA_HIP(hipMalloc((void**)&s.d_sc, sizeof(BaScalars)));
-        BA_HIP(hipHostMalloc((void**)&s.h_sc, sizeof(BaScalars), hipHostMallocDefault));
-    }
-    if (A.used > s.cap) {
-        if (s.d_mem) (void)hipFree(s.d_mem);
-        s.d_mem = nullptr; s.cap = 0;
-        BA_HIP(hipMalloc((void**)&s.d_mem, A.used));
-        s.cap = A.used;
-    }
-    if (upload > s.h_cap) {
-        if (s.h_mem) (void)hipHostFree(s.h_mem);
-        s.h_mem = nullptr; s.h_cap = 0;
-        BA_HIP(hipHostMalloc((void**)&s.h_mem, upload, hipHostMallocDefault));
-        s.h_cap = upload;
-    }
+    BaState& s = *static_cast<BaState*>(state);
+    MI_HIP(s.d_sc.need(sizeof(BaScalars)));
+    MI_HIP(s.h_sc.need(sizeof(BaScalars)));
+    MI_HIP(s.d_mem.need(A.used));
+    MI_HIP(s.h_mem.need(upload));
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
+    uint8_t* const h_mem = (uint8_t*)s.h_mem.p;
+    BaScalars* const d_sc = (BaScalars*)s.d_sc.p;
+    const BaScalars* const h_sc = (const BaScalars*)s.h_sc.p;
 
     /* two stable counting sorts: observations by point (slots), slots by camera (cpos) */
-    int32_t* pt_ptr = (int32_t*)(s.h_mem + o_pt_ptr);
-    int32_t* cam_ptr = (int32_t*)(s.h_mem + o_cam_ptr);
-    int32_t* s_cam = (int32_t*)(s.h_mem + o_s_cam);
-    int32_t* s_pt = (int32_t*)(s.h_mem + o_s_pt);
-    int32_t* s_cpos = (int32_t*)(s.h_mem + o_s_cpos);
-    double* s_xy = (double*)(s.h_mem + o_s_xy);
+    int32_t* pt_ptr = (int32_t*)(h_mem + o_pt_ptr);
+    int32_t* cam_ptr = (int32_t*)(h_mem + o_cam_ptr);
+    int32_t* s_cam = (int32_t*)(h_mem + o_s_cam);
+    int32_t* s_pt = (int32_t*)(h_mem + o_s_pt);
+    int32_t* s_cpos = (int32_t*)(h_mem + o_s_cpos);
+    double* s_xy = (double*)(h_mem + o_s_xy);
     std::fill(pt_ptr, pt_ptr + npt + 1, 0);
     std::fill(cam_ptr, cam_ptr + ncam + 1, 0);
     for (size_t i = 0; i < n; ++i) { ++pt_ptr[obs[i].point_id + 1]; ++cam_ptr[obs[i].camera_id + 1]; }
@@ -165,9 +124,9 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
         next.assign(cam_ptr, cam_ptr + ncam);
         for (size_t slot = 0; slot < n; ++slot) s_cpos[slot] = next[s_cam[slot]]++;
     }
-    int32_t* h_const = (int32_t*)(s.h_mem + o_const);
-    double* h_cam = (double*)(s.h_mem + o_cam0);
-    double* h_pt = (double*)(s.h_mem + o_pt0);
+    int32_t* h_const = (int32_t*)(h_mem + o_const);
+    double* h_cam = (double*)(h_mem + o_cam0);
+    double* h_pt = (double*)(h_mem + o_pt0);
     for (size_t p = 0; p < npt; ++p) {
         h_const[p] = pts[p].is_constant != 0;
         for (int k = 0; k < 3; ++k) h_pt[k * npt + p] = pts[p].pos[k];
@@ -178,9 +137,9 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
         for (int k = 0; k < 3; ++k) q[3 + k] = cams[c].translation[k];
         for (int k = 0; k < 9; ++k) q[6 + k] = cams[c].rotation[k];
     }
-    BA_HIP(hipMemcpyAsync(s.d_mem, s.h_mem, upload, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(s.d_mem.p, h_mem, upload, hipMemcpyHostToDevice, stream));
 
-    uint8_t* m = s.d_mem;
+    uint8_t* m = (uint8_t*)s.d_mem.p;
     BaProblem P;
     P.n_cam = nc; P.n_pt = np; P.n_obs = no;
     P.pt_ptr = (const int32_t*)(m + o_pt_ptr); P.cam_ptr = (const int32_t*)(m + o_cam_ptr);
@@ -194,11 +153,11 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
     W.dz = (double*)(m + o_dz); W.B = (double*)(m + o_B); W.P = (double*)(m + o_P);
     W.Bdiag = (double*)(m + o_vec[0]); W.v = (double*)(m + o_vec[1]); W.x = (double*)(m + o_vec[2]); W.r = (double*)(m + o_vec[3]);
     W.d = (double*)(m + o_vec[4]); W.z = (double*)(m + o_vec[5]); W.Ad = (double*)(m + o_vec[6]);
-    W.cam_part = (double*)(m + o_cam_part); W.blk_part = (double*)(m + o_blk); W.sc = s.d_sc;
+    W.cam_part = (double*)(m + o_cam_part); W.blk_part = (double*)(m + o_blk); W.sc = d_sc;
 
     auto read_scalars = [&]() -> hipError_t {
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(s.h_sc, s.d_sc, sizeof(BaScalars), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.h_sc.p, d_sc, sizeof(BaScalars), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         return e;
     };
@@ -208,8 +167,8 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
     st.radius = 1000.0;                                          /* TRUST_REGION_RADIUS_INIT */
 
     mi_ba_launch_residual(stream, P, cur, W);
-    BA_HIP(read_scalars());
-    double current_mse = s.h_sc->mse;
+    MI_HIP(read_scalars());
+    double current_mse = h_sc->mse;
     mi_dmrecon_ba_status out;
     std::memset(&out, 0, sizeof(out));
     out.initial_mse = current_mse;
@@ -228,16 +187,16 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
                 const int32_t batch = std::min<int32_t>(BA_CG_BATCH, st.cg_max - enqueued);
                 mi_ba_launch_cg(st, P, W, batch);
                 enqueued += batch;
-                BA_HIP(read_scalars());
-                if (s.h_sc->done) break;
+                MI_HIP(read_scalars());
+                if (h_sc->done) break;
             }
-            cg_iterations = s.h_sc->iter;
+            cg_iterations = h_sc->iter;
         }
         mi_ba_launch_finish(st, P, cur, cand, W);
-        BA_HIP(read_scalars());
+        MI_HIP(read_scalars());
 
         /* (the reference's CG cannot fail on these inputs: its sizes always agree, ba_conjugate_gradient.h:126-130) */
-        const double new_mse = s.h_sc->mse;
+        const double new_mse = h_sc->mse;
         const double delta_mse = current_mse - new_mse;
         const double delta_mse_ratio = 1.0 - new_mse / current_mse;
         out.num_cg_iterations += cg_iterations;
@@ -253,7 +212,7 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
             std::swap(cur, cand);
             jacobian = true;
             current_mse = new_mse;
-            const double gain_ratio = delta_mse * (double)no / s.h_sc->pred;
+            const double gain_ratio = delta_mse * (double)no / h_sc->pred;
             const double c3 = 2.0 * gain_ratio - 1.0;
             st.radius *= 1.0 / std::max(1.0 / 3.0, 1.0 - c3 * c3 * c3);
         } else {
@@ -268,9 +227,9 @@ int ba_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* o, int32_t nc, mi_
     out.final_mse = current_mse;
 
     /* the current set comes back through the pinned mirror */
-    BA_HIP(hipMemcpyAsync(h_cam, cur.cam, ncam * BA_CAM_DOUBLES * 8, hipMemcpyDeviceToHost, stream));
-    BA_HIP(hipMemcpyAsync(h_pt, cur.pt, 3 * npt * 8, hipMemcpyDeviceToHost, stream));
-    BA_HIP(hipStreamSynchronize(stream));
+    MI_HIP(hipMemcpyAsync(h_cam, cur.cam, ncam * BA_CAM_DOUBLES * 8, hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipMemcpyAsync(h_pt, cur.pt, 3 * npt * 8, hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipStreamSynchronize(stream));
     for (size_t c = 0; c < ncam; ++c) {
         const double* q = h_cam + c * BA_CAM_DOUBLES;
         cams[c].focal_length = q[0]; cams[c].distortion[0] = q[1]; cams[c].distortion[1] = q[2];
@@ -303,8 +262,7 @@ int mi_dmrecon_ba_optimize(mi_dmrecon_ctx* ctx, const mi_dmrecon_ba_options* opt
                            int32_t n_points, mi_dmrecon_ba_point* points, int32_t n_observations,
                            const mi_dmrecon_ba_observation* observations, mi_dmrecon_ba_status* status, mi_dmrecon_ba_trace* trace,
                            int32_t trace_capacity) {
-    try { return ba_impl(ctx, options, n_cameras, cameras, n_points, points, n_observations, observations, status, trace, trace_capacity); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return ba_impl(ctx, options, n_cameras, cameras, n_points, points, n_observations, observations, status, trace, trace_capacity); });
 }
 
 }  /* extern "C" */

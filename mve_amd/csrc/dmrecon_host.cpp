@@ -44,6 +44,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "host_common.h"
 #include "dmrecon_device.h"
 #include "pointset_device.h"
 #include "gvs_device.h"
@@ -464,11 +465,6 @@ struct SceneStore {
     }
 };
 
-void mi_ransac_release(struct RansacState* s);   /* ransac_host.cpp */
-void mi_sift_release(struct SiftState* s);       /* sift_host.cpp */
-void mi_surf_release(struct SurfState* s);       /* surf_host.cpp */
-void mi_ba_release(struct BaState* s);           /* ba_host.cpp */
-
 struct mi_dmrecon_ctx {
     int device = 0;
     int n_cus = 64;                          /* compute units (queried at creation) */
@@ -484,10 +480,9 @@ struct mi_dmrecon_ctx {
     DevBuf<uint8_t> d_stage2;
     int stage_flip = 0;
     BatchScratch bs;                         /* leased from the scene's pool for the duration of a call (ScratchLease) */
-    struct RansacState* ransac = nullptr;    /* buffers of mi_dmrecon_ransac_fundamental (ransac_host.cpp), made by its first call */
-    struct SiftState* sift = nullptr;        /* buffers and last results of mi_dmrecon_sift_run (sift_host.cpp), likewise */
-    struct SurfState* surf = nullptr;        /* ... and of mi_dmrecon_surf_run (surf_host.cpp) */
-    struct BaState* ba = nullptr;            /* ... and of mi_dmrecon_ba_optimize (ba_host.cpp) */
+    /* buffers and last results of the RANSAC, SIFT, SURF and BA entry points ({ransac,sift,surf,ba}_host.cpp), each made by
+     * its module's first call on this context */
+    HostModule* modules[MI_MODULE_COUNT] = {};
 };
 
 namespace {
@@ -1498,10 +1493,7 @@ void mi_dmrecon_ctx_destroy(mi_dmrecon_ctx* c) {
     if (c->stream2) (void)wait_stream(c->stream2);
     c->bs.release();
     c->d_stage.release(); c->d_stage2.release();
-    mi_ransac_release(c->ransac);
-    mi_sift_release(c->sift);
-    mi_surf_release(c->surf);
-    mi_ba_release(c->ba);
+    for (HostModule* m : c->modules) delete m;
     if (c->d_counters) (void)hipFree(c->d_counters);
     (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -3556,8 +3548,7 @@ int mi_dmrecon_debug_buffer(unsigned long long* out, int n) {
 
 /* ---- the entry points that allocate host memory: no exception crosses the C ABI (std::bad_alloc -> MI_DMRECON_EDEVICE) */
 int mi_dmrecon_global_view_selection(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, int32_t ref_view, int32_t* ids_out, int32_t* n_out) {
-    try { return mi_dmrecon_global_view_selection_impl(c, st, ref_view, ids_out, n_out); }
-    catch (const std::bad_alloc&) { return fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return mi_dmrecon_global_view_selection_impl(c, st, ref_view, ids_out, n_out); });
 }
 
 int mi_dmrecon_reconstruct(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, int32_t n_refs, const int32_t* ref_views, mi_dmrecon_maps* maps, mi_dmrecon_progress* progress, int32_t* status_out, mi_dmrecon_stats* stats) {
@@ -3571,39 +3562,30 @@ int mi_dmrecon_reconstruct(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, int
             return fail(MI_DMRECON_EINVAL, "mi_dmrecon_stats::struct_size must be set to sizeof(mi_dmrecon_stats) before the call");
         room = std::min((size_t)stats->struct_size, sizeof(full));
     }
-    int rc;
-    try { rc = mi_dmrecon_reconstruct_impl(c, st, n_refs, ref_views, maps, progress, status_out, stats ? &full : nullptr); }
-    catch (const std::bad_alloc&) { rc = fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    const int rc = guarded([&] { return mi_dmrecon_reconstruct_impl(c, st, n_refs, ref_views, maps, progress, status_out, stats ? &full : nullptr); });
     if (stats) { full.struct_size = (int64_t)room; std::memcpy(stats, &full, room); }
     return rc;
 }
 
 int mi_dmrecon_patch_optimize(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, int32_t ref_view, int32_t n, const int32_t* xy, const float* hyp, const int32_t* local, int32_t lanes_per_view, float* out, int32_t* out_local) {
-    try { return mi_dmrecon_patch_optimize_impl(c, st, ref_view, n, xy, hyp, local, lanes_per_view, out, out_local); }
-    catch (const std::bad_alloc&) { return fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return mi_dmrecon_patch_optimize_impl(c, st, ref_view, n, xy, hyp, local, lanes_per_view, out, out_local); });
 }
 
 int mi_dmrecon_patch_eval(mi_dmrecon_ctx* c, const mi_dmrecon_settings* st, int32_t ref_view, int32_t x, int32_t y, float depth, float dzI, float dzJ, float* master, float* ncc, int32_t* ok, float* col, float* deriv, int32_t* level) {
-    try { return mi_dmrecon_patch_eval_impl(c, st, ref_view, x, y, depth, dzI, dzJ, master, ncc, ok, col, deriv, level); }
-    catch (const std::bad_alloc&) { return fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return mi_dmrecon_patch_eval_impl(c, st, ref_view, x, y, depth, dzI, dzJ, master, ncc, ok, col, deriv, level); });
 }
 
 int mi_dmrecon_set_features(mi_dmrecon_ctx* c, int32_t n, const float* pos, const int32_t* off, const int32_t* ids) {
-    try { return mi_dmrecon_set_features_impl(c, n, pos, off, ids); }
-    catch (const std::bad_alloc&) { return fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return mi_dmrecon_set_features_impl(c, n, pos, off, ids); });
 }
 
 int mi_dmrecon_pointset(mi_dmrecon_ctx* c, const mi_dmrecon_camera* cam, int32_t w, int32_t h, const float* depth, const uint8_t* color, int32_t color_channels, const mi_dmrecon_pointset_options* opt, int32_t capacity, int32_t* pixel, float* pos, float* normal, float* color_out, float* scale, float* conf, int32_t* n_out) {
-    try { return mi_dmrecon_pointset_impl(c, cam, w, h, depth, color, color_channels, opt, capacity, pixel, pos, normal, color_out, scale, conf, n_out); }
-    catch (const std::bad_alloc&) { return fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return mi_dmrecon_pointset_impl(c, cam, w, h, depth, color, color_channels, opt, capacity, pixel, pos, normal, color_out, scale, conf, n_out); });
 }
 
 }  /* extern "C" */
 
-/* for the other host sources of the library (fssr_host.cpp); not exported (exports.map) */
+/* host_common.h: for the other host sources of the library; not exported (exports.map) */
 int mi_host_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int mi_host_ctx_device(const mi_dmrecon_ctx* c) { return c ? c->device : -1; }
-RansacState** mi_host_ctx_ransac(mi_dmrecon_ctx* c) { return &c->ransac; }
-SiftState** mi_host_ctx_sift(mi_dmrecon_ctx* c) { return &c->sift; }
-SurfState** mi_host_ctx_surf(mi_dmrecon_ctx* c) { return &c->surf; }
-BaState** mi_host_ctx_ba(mi_dmrecon_ctx* c) { return &c->ba; }
+HostModule*& mi_host_ctx_module(mi_dmrecon_ctx* c, int which) { return c->modules[which]; }

@@ -12,12 +12,8 @@
 #include <new>
 #include <vector>
 
-#include "../../include/mi_dmrecon.h"
+#include "host_common.h"
 #include "fssr_device.h"
-
-/* dmrecon_host.cpp: the thread-local error message and the context's device (not exported, exports.map) */
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
 
 static_assert(sizeof(mi_dmrecon_fssr_sample_t) == sizeof(FssrSample) && sizeof(FssrSample) == 44, "sample layout");
 static_assert(sizeof(mi_dmrecon_fssr_node) == sizeof(FssrNode) && sizeof(FssrNode) == 16, "node layout");
@@ -31,32 +27,15 @@ struct mi_dmrecon_fssr {
     FssrNode* d_nodes = nullptr;
     FssrLists lists{};             /* the part of the wavefronts' lists that does not fit their LDS */
     /* per-chunk buffers, grown on demand */
-    int64_t chunk_cap = 0;
-    double* d_pos = nullptr;
-    float* d_f = nullptr;          /* value, conf, scale, max_scale: 4 x cap; color, deriv: 2 x 3 x cap */
-    int32_t* d_n = nullptr;
+    Buf d_pos;                     /* double: 3 x cap */
+    Buf d_f;                       /* float: value, conf, scale, max_scale: 4 x cap; color, deriv: 2 x 3 x cap */
+    Buf d_n;                       /* int32_t: cap */
 };
 
 namespace {
 
 #define FSSR_CHUNK (1 << 18)       /* voxels per launch */
 #define FSSR_MAX_COUNT (1 << 30)   /* samples / nodes: indices stay far inside int32 */
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), fmt, a, b);
-    return mi_host_fail(code, buf);
-}
-
-#define FSSR_HIP(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
 
 /* Everything the kernel relies on: children after parents (so the walk terminates), eight consecutive children inside the
  * array, sample ranges inside the samples, at most FSSR_MAX_LEVELS levels. */
@@ -99,10 +78,7 @@ void release(mi_dmrecon_fssr* f) {
     if (f->d_samples) (void)hipFree(f->d_samples);
     if (f->d_nodes) (void)hipFree(f->d_nodes);
     if (f->lists.entries) (void)hipFree(f->lists.entries);
-    if (f->d_pos) (void)hipFree(f->d_pos);
-    if (f->d_f) (void)hipFree(f->d_f);
-    if (f->d_n) (void)hipFree(f->d_n);
-    delete f;
+    delete f;                      /* (the per-chunk buffers go with it) */
 }
 
 int create_impl(mi_dmrecon_ctx* ctx, int64_t n_samples, const mi_dmrecon_fssr_sample_t* samples, int64_t n_nodes,
@@ -112,7 +88,7 @@ int create_impl(mi_dmrecon_ctx* ctx, int64_t n_samples, const mi_dmrecon_fssr_sa
     if (int rc = validate(n_samples, samples, n_nodes, nodes, root_center, root_size)) return rc;
     const int device = mi_host_ctx_device(ctx);
     if (device < 0) return failf(MI_DMRECON_EINVAL, "fssr: the context has no device");
-    FSSR_HIP(hipSetDevice(device));
+    MI_HIP(hipSetDevice(device));
     mi_dmrecon_fssr* f = new mi_dmrecon_fssr();
     f->ctx = ctx; f->device = device; f->stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
     f->tree.n_samples = (int32_t)n_samples; f->tree.n_nodes = (int32_t)n_nodes;
@@ -152,35 +128,30 @@ int sample_impl(mi_dmrecon_fssr* f, const mi_dmrecon_fssr_options* opt, int64_t 
     int32_t cap = opt ? opt->list_capacity : 0;
     if (cap < 0) return failf(MI_DMRECON_EINVAL, "fssr: negative list_capacity");
     if (cap == 0) cap = FSSR_LIST_MAX + FSSR_GLIST_MAX;        /* (the launcher clamps it to what the lists hold) */
-    FSSR_HIP(hipSetDevice(f->device));
+    MI_HIP(hipSetDevice(f->device));
     const int64_t chunk = n_voxels < FSSR_CHUNK ? n_voxels : FSSR_CHUNK;
-    if (chunk > f->chunk_cap) {
-        if (f->d_pos) (void)hipFree(f->d_pos);
-        if (f->d_f) (void)hipFree(f->d_f);
-        if (f->d_n) (void)hipFree(f->d_n);
-        f->d_pos = nullptr; f->d_f = nullptr; f->d_n = nullptr; f->chunk_cap = 0;
-        FSSR_HIP(hipMalloc((void**)&f->d_pos, (size_t)chunk * 3 * sizeof(double)));
-        FSSR_HIP(hipMalloc((void**)&f->d_f, (size_t)chunk * 10 * sizeof(float)));
-        FSSR_HIP(hipMalloc((void**)&f->d_n, (size_t)chunk * sizeof(int32_t)));
-        f->chunk_cap = chunk;
-    }
-    const size_t C = (size_t)f->chunk_cap;
+    MI_HIP(f->d_pos.need((size_t)chunk * 3 * sizeof(double)));
+    MI_HIP(f->d_f.need((size_t)chunk * 10 * sizeof(float)));
+    MI_HIP(f->d_n.need((size_t)chunk * sizeof(int32_t)));
+    const size_t C = f->d_f.cap / (10 * sizeof(float));          /* the chunk d_f was made for: its layout */
+    double* const d_pos = (double*)f->d_pos.p;
+    float* const d_f = (float*)f->d_f.p;
     FssrOut o;
-    o.value = f->d_f; o.conf = f->d_f + C; o.scale = f->d_f + 2 * C; o.max_scale = f->d_f + 3 * C;
-    o.color = f->d_f + 4 * C; o.deriv = f->d_f + 7 * C; o.n_influencing = f->d_n;
+    o.value = d_f; o.conf = d_f + C; o.scale = d_f + 2 * C; o.max_scale = d_f + 3 * C;
+    o.color = d_f + 4 * C; o.deriv = d_f + 7 * C; o.n_influencing = (int32_t*)f->d_n.p;
     for (int64_t v0 = 0; v0 < n_voxels; v0 += chunk) {
         const size_t m = (size_t)(n_voxels - v0 < chunk ? n_voxels - v0 : chunk);
-        FSSR_HIP(hipMemcpyAsync(f->d_pos, positions + 3 * v0, m * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-        mi_fssr_launch(f->stream, f->tree, cap, f->lists, (int32_t)m, f->d_pos, o);
-        FSSR_HIP(hipGetLastError());
-        if (value) FSSR_HIP(hipMemcpyAsync(value + v0, o.value, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (conf) FSSR_HIP(hipMemcpyAsync(conf + v0, o.conf, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (scale) FSSR_HIP(hipMemcpyAsync(scale + v0, o.scale, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (max_scale) FSSR_HIP(hipMemcpyAsync(max_scale + v0, o.max_scale, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (color) FSSR_HIP(hipMemcpyAsync(color + 3 * v0, o.color, m * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (deriv) FSSR_HIP(hipMemcpyAsync(deriv + 3 * v0, o.deriv, m * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
-        if (n_influencing) FSSR_HIP(hipMemcpyAsync(n_influencing + v0, o.n_influencing, m * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-        FSSR_HIP(hipStreamSynchronize(f->stream));
+        MI_HIP(hipMemcpyAsync(d_pos, positions + 3 * v0, m * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+        mi_fssr_launch(f->stream, f->tree, cap, f->lists, (int32_t)m, d_pos, o);
+        MI_HIP(hipGetLastError());
+        if (value) MI_HIP(hipMemcpyAsync(value + v0, o.value, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (conf) MI_HIP(hipMemcpyAsync(conf + v0, o.conf, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (scale) MI_HIP(hipMemcpyAsync(scale + v0, o.scale, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (max_scale) MI_HIP(hipMemcpyAsync(max_scale + v0, o.max_scale, m * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (color) MI_HIP(hipMemcpyAsync(color + 3 * v0, o.color, m * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (deriv) MI_HIP(hipMemcpyAsync(deriv + 3 * v0, o.deriv, m * 3 * sizeof(float), hipMemcpyDeviceToHost, f->stream));
+        if (n_influencing) MI_HIP(hipMemcpyAsync(n_influencing + v0, o.n_influencing, m * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+        MI_HIP(hipStreamSynchronize(f->stream));
     }
     return 0;
 }
@@ -195,8 +166,7 @@ void mi_dmrecon_fssr_options_default(mi_dmrecon_fssr_options* o) {
 
 int mi_dmrecon_fssr_create(mi_dmrecon_ctx* ctx, int64_t n_samples, const mi_dmrecon_fssr_sample_t* samples, int64_t n_nodes,
                            const mi_dmrecon_fssr_node* nodes, const double root_center[3], double root_size, mi_dmrecon_fssr** out) {
-    try { return create_impl(ctx, n_samples, samples, n_nodes, nodes, root_center, root_size, out); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return create_impl(ctx, n_samples, samples, n_nodes, nodes, root_center, root_size, out); });
 }
 
 int mi_dmrecon_fssr_sample(mi_dmrecon_fssr* f, const mi_dmrecon_fssr_options* opt, int64_t n_voxels, const double* positions,

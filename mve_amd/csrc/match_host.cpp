@@ -14,13 +14,9 @@
 #include <new>
 #include <vector>
 
-#include "../../include/mi_dmrecon.h"
 #include "../../include/mi_dmrecon_debug.h"
+#include "host_common.h"
 #include "match_device.h"
-
-/* dmrecon_host.cpp: the thread-local error message and the context's device (not exported, exports.map) */
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
 
 static_assert(MI_DMRECON_MATCH_SIFT == MATCH_SIFT && MI_DMRECON_MATCH_SURF == MATCH_SURF, "descriptor kinds");
 
@@ -43,11 +39,10 @@ struct MatchSet {
 struct MatchSlot {
     hipStream_t stream = nullptr;
     bool busy = false;
-    size_t jobs_cap = 0, entries_cap = 0;
-    MatchJobDev* d_jobs = nullptr;
-    unsigned long long* d_best = nullptr;
-    int32_t* d_matches = nullptr;
-    int32_t* h_matches = nullptr;            /* pinned */
+    Buf d_jobs;                              /* MatchJobDev per job */
+    Buf d_best;                              /* two unsigned long long per row and column ... */
+    Buf d_matches;                           /* ... and one int32_t */
+    PinnedBuf h_matches;
 };
 
 }  /* namespace */
@@ -62,22 +57,6 @@ struct mi_dmrecon_match {
 };
 
 namespace {
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0, long long c = 0) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return mi_host_fail(code, buf);
-}
-
-#define MATCH_HIP(expr)                                                                       \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
 
 int dims_of(int kind) { return kind == MATCH_SIFT ? 128 : 64; }
 
@@ -94,12 +73,8 @@ void release(mi_dmrecon_match* m) {
         for (MatchSet& s : m->sets[k]) free_set(s);
     for (MatchSlot& s : m->slots) {
         if (s.stream) { (void)hipStreamSynchronize(s.stream); (void)hipStreamDestroy(s.stream); }
-        if (s.d_jobs) (void)hipFree(s.d_jobs);
-        if (s.d_best) (void)hipFree(s.d_best);
-        if (s.d_matches) (void)hipFree(s.d_matches);
-        if (s.h_matches) (void)hipHostFree(s.h_matches);
     }
-    delete m;
+    delete m;                                /* (the slots' buffers go with it) */
 }
 
 /* A free slot for the length of a call. */
@@ -127,7 +102,7 @@ int create_impl(mi_dmrecon_ctx* ctx, int32_t n_sets, mi_dmrecon_match** out) {
     if (!ctx) return failf(MI_DMRECON_EINVAL, "match: null context");
     const int device = mi_host_ctx_device(ctx);
     if (device < 0) return failf(MI_DMRECON_EINVAL, "match: the context has no device");
-    MATCH_HIP(hipSetDevice(device));
+    MI_HIP(hipSetDevice(device));
     mi_dmrecon_match* m = new mi_dmrecon_match();
     m->device = device; m->n_sets = n_sets;
     m->sets[0].resize(n_sets); m->sets[1].resize(n_sets);
@@ -170,7 +145,7 @@ int set_impl(mi_dmrecon_match* m, int32_t set, int32_t kind, int32_t dtype, int3
     }
 
     std::lock_guard<std::mutex> lock(m->mu);
-    MATCH_HIP(hipSetDevice(m->device));
+    MI_HIP(hipSetDevice(m->device));
     MatchSet& s = m->sets[kind][set];
     free_set(s);
     if (n == 0) return 0;
@@ -210,24 +185,12 @@ int count_consistent(const int32_t* ab, int32_t n_a, const int32_t* ba) {   /* M
 }
 
 int grow(MatchSlot& s, size_t n_jobs, size_t n_entries) {
-    if (!s.stream) MATCH_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    if (n_jobs > s.jobs_cap) {
-        if (s.d_jobs) (void)hipFree(s.d_jobs);
-        s.d_jobs = nullptr; s.jobs_cap = 0;
-        const size_t cap = std::max<size_t>(n_jobs, 256);
-        MATCH_HIP(hipMalloc((void**)&s.d_jobs, cap * sizeof(MatchJobDev)));
-        s.jobs_cap = cap;
-    }
-    if (n_entries > s.entries_cap) {
-        if (s.d_best) (void)hipFree(s.d_best);
-        if (s.d_matches) (void)hipFree(s.d_matches);
-        if (s.h_matches) (void)hipHostFree(s.h_matches);
-        s.d_best = nullptr; s.d_matches = nullptr; s.h_matches = nullptr; s.entries_cap = 0;
-        MATCH_HIP(hipMalloc((void**)&s.d_best, n_entries * 2 * sizeof(unsigned long long)));
-        MATCH_HIP(hipMalloc((void**)&s.d_matches, n_entries * sizeof(int32_t)));
-        MATCH_HIP(hipHostMalloc((void**)&s.h_matches, n_entries * sizeof(int32_t), hipHostMallocDefault));
-        s.entries_cap = n_entries;
-    }
+    if (!s.stream) MI_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    MI_HIP(s.d_jobs.need(std::max<size_t>(n_jobs, 256) * sizeof(MatchJobDev)));
+    /* (the three are asked for the same number of entries every time, so they grow together) */
+    MI_HIP(s.d_best.need(n_entries * 2 * sizeof(unsigned long long)));
+    MI_HIP(s.d_matches.need(n_entries * sizeof(int32_t)));
+    MI_HIP(s.h_matches.need(n_entries * sizeof(int32_t)));
     return 0;
 }
 
@@ -306,7 +269,7 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
 
     SlotLease lease(m);
     MatchSlot& s = *lease.slot;
-    MATCH_HIP(hipSetDevice(m->device));
+    MI_HIP(hipSetDevice(m->device));
     std::vector<MatchJobDev> dev;
     std::vector<int32_t> which;
     int32_t j = 0;
@@ -326,16 +289,16 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
         }
         if (dev.empty()) break;
         if (int rc = grow(s, dev.size(), (size_t)entries)) return rc;
-        MATCH_HIP(hipMemcpyAsync(s.d_jobs, dev.data(), dev.size() * sizeof(MatchJobDev), hipMemcpyHostToDevice, s.stream));
-        MATCH_HIP(hipMemsetAsync(s.d_best, 0, (size_t)entries * 2 * sizeof(unsigned long long), s.stream));
-        mi_match_launch(s.stream, kind, s.d_jobs, (int32_t)dev.size(), (int32_t)blocks, entries, s.d_best, s.d_matches,
-                        square_lowe_thres, square_dist_thres);
-        MATCH_HIP(hipGetLastError());
-        MATCH_HIP(hipMemcpyAsync(s.h_matches, s.d_matches, (size_t)entries * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
-        MATCH_HIP(hipStreamSynchronize(s.stream));       /* (before `dev` changes: the copy above may still read it) */
+        MI_HIP(hipMemcpyAsync(s.d_jobs.p, dev.data(), dev.size() * sizeof(MatchJobDev), hipMemcpyHostToDevice, s.stream));
+        MI_HIP(hipMemsetAsync(s.d_best.p, 0, (size_t)entries * 2 * sizeof(unsigned long long), s.stream));
+        mi_match_launch(s.stream, kind, (const MatchJobDev*)s.d_jobs.p, (int32_t)dev.size(), (int32_t)blocks, entries,
+                        (unsigned long long*)s.d_best.p, (int32_t*)s.d_matches.p, square_lowe_thres, square_dist_thres);
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipMemcpyAsync(s.h_matches.p, s.d_matches.p, (size_t)entries * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
+        MI_HIP(hipStreamSynchronize(s.stream));       /* (before `dev` changes: the copy above may still read it) */
         for (size_t k = 0; k < dev.size(); ++k) {
             const int32_t jj = which[k];
-            const int32_t* ab = s.h_matches + dev[k].entry0;
+            const int32_t* ab = (const int32_t*)s.h_matches.p + dev[k].entry0;
             const int32_t* ba = ab + dev[k].n_a;
             if (matches_ab && matches_ab[jj]) std::memcpy(matches_ab[jj], ab, (size_t)dev[k].n_a * sizeof(int32_t));
             if (matches_ba && matches_ba[jj]) std::memcpy(matches_ba[jj], ba, (size_t)dev[k].n_b * sizeof(int32_t));
@@ -350,20 +313,17 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
 extern "C" {
 
 int mi_dmrecon_match_create(mi_dmrecon_ctx* ctx, int32_t n_sets, mi_dmrecon_match** out) {
-    try { return create_impl(ctx, n_sets, out); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return create_impl(ctx, n_sets, out); });
 }
 
 int mi_dmrecon_match_set(mi_dmrecon_match* m, int32_t set, int32_t kind, int32_t dtype, int32_t n, const void* descriptors) {
-    try { return set_impl(m, set, kind, dtype, n, descriptors); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return set_impl(m, set, kind, dtype, n, descriptors); });
 }
 
 int mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs,
                            const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
                            int32_t* n_consistent) {
-    try { return pairs_impl(m, kind, opt, n_jobs, jobs, matches_ab, matches_ba, n_consistent); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return pairs_impl(m, kind, opt, n_jobs, jobs, matches_ab, matches_ba, n_consistent); });
 }
 
 void mi_dmrecon_match_destroy(mi_dmrecon_match* m) { release(m); }
@@ -377,9 +337,9 @@ int mi_dmrecon_debug_match_get(mi_dmrecon_match* m, int32_t set, int32_t kind, i
     std::lock_guard<std::mutex> lock(m->mu);
     const MatchSet& s = m->sets[kind][set];
     if (s.n == 0) return 0;
-    MATCH_HIP(hipSetDevice(m->device));
-    if (bytes_out) MATCH_HIP(hipMemcpy(bytes_out, s.d_desc, (size_t)s.n * dims_of(kind), hipMemcpyDeviceToHost));
-    if (off_out) MATCH_HIP(hipMemcpy(off_out, s.d_off, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    MI_HIP(hipSetDevice(m->device));
+    if (bytes_out) MI_HIP(hipMemcpy(bytes_out, s.d_desc, (size_t)s.n * dims_of(kind), hipMemcpyDeviceToHost));
+    if (off_out) MI_HIP(hipMemcpy(off_out, s.d_off, (size_t)s.n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return s.n;
 }
 
@@ -394,7 +354,7 @@ int mi_dmrecon_debug_match_limits(long long entries, long long blocks) {
 
 int mi_dmrecon_debug_match_plan(int32_t n_jobs, const int32_t* n_a, const int32_t* n_b, long long entries, long long blocks,
                                 int32_t* batch_out, int32_t* block0_out, int32_t* col_chunks_out, int64_t* entry0_out) {
-    try {
+    return guarded([&] {
         if (n_jobs < 0 || (n_jobs > 0 && (!n_a || !n_b))) return failf(MI_DMRECON_EINVAL, "match: a negative number of jobs or no sizes");
         if (entries < 0 || blocks < 0) return failf(MI_DMRECON_EINVAL, "match: negative limits");
         for (int32_t j = 0; j < n_jobs; ++j)
@@ -410,8 +370,7 @@ int mi_dmrecon_debug_match_plan(int32_t n_jobs, const int32_t* n_a, const int32_
             if (entry0_out) entry0_out[j] = plan[j].entry0;
         }
         return n_batches;
-    }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    });
 }
 
 }  /* extern "C" */

@@ -13,58 +13,23 @@
 #include <new>
 #include <vector>
 
-#include "../../include/mi_dmrecon.h"
+#include "host_common.h"
 #include "ransac_device.h"
-
-/* dmrecon_host.cpp (not exported, exports.map): the thread-local error message, and the context's device and RANSAC state */
-struct RansacState;
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
-RansacState** mi_host_ctx_ransac(mi_dmrecon_ctx* c);
-
-/* The buffers of a context's calls; they grow only and go with the context (mi_ransac_release). */
-struct RansacState {
-    size_t in_cap = 0, out_cap = 0;
-    uint8_t* d_in = nullptr;                 /* jobs | list | samples */
-    uint8_t* h_in = nullptr;                 /* pinned, the same layout */
-    uint8_t* d_out = nullptr;                /* best_model | best | inliers | counts | hyp_all */
-    uint8_t* h_out = nullptr;                /* pinned */
-    unsigned long long* d_capped = nullptr;
-    unsigned long long capped = 0;           /* as of the last call */
-};
-
-void mi_ransac_release(RansacState* s) {
-    if (!s) return;
-    if (s->d_in) (void)hipFree(s->d_in);
-    if (s->h_in) (void)hipHostFree(s->h_in);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->d_capped) (void)hipFree(s->d_capped);
-    delete s;
-}
 
 namespace {
 
+/* The buffers of a context's calls; they grow only and go with the context. */
+struct RansacState : HostModule {
+    Buf d_in;                                /* jobs | list | samples */
+    PinnedBuf h_in;                          /* the same layout */
+    Buf d_out;                               /* best_model | best | inliers | counts | hyp_all */
+    PinnedBuf h_out;
+    Buf d_capped;                            /* one unsigned long long, zeroed when it is made */
+    unsigned long long capped = 0;           /* as of the last call */
+};
+
 #define RANSAC_MAX_HYP (1ll << 30)           /* hypotheses / matches of a call: indices stay far inside int32 / the buffers small */
 #define RANSAC_MAX_BLOCKS ((1ll << 24) - 1)  /* workgroups of a launch */
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0, long long c = 0) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return mi_host_fail(code, buf);
-}
-
-#define RANSAC_HIP(expr)                                                                      \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
-
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 /* What the host has to know of a model (ransac_device.h has the kernels' side). */
 struct Model {
@@ -169,26 +134,15 @@ int plan(const std::vector<Job>& jobs, int sample, int entry_dev, int per_iterat
 }
 
 int grow(RansacState& s, size_t in_bytes, size_t out_bytes) {
-    if (!s.d_capped) {
-        RANSAC_HIP(hipMalloc((void**)&s.d_capped, sizeof(unsigned long long)));
-        RANSAC_HIP(hipMemset(s.d_capped, 0, sizeof(unsigned long long)));
+    if (!s.d_capped.p) {
+        MI_HIP(s.d_capped.need(sizeof(unsigned long long)));
+        MI_HIP(hipMemset(s.d_capped.p, 0, sizeof(unsigned long long)));
     }
-    if (in_bytes > s.in_cap) {
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        s.d_in = nullptr; s.h_in = nullptr; s.in_cap = 0;
-        RANSAC_HIP(hipMalloc((void**)&s.d_in, in_bytes));
-        RANSAC_HIP(hipHostMalloc((void**)&s.h_in, in_bytes, hipHostMallocDefault));
-        s.in_cap = in_bytes;
-    }
-    if (out_bytes > s.out_cap) {
-        if (s.d_out) (void)hipFree(s.d_out);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        s.d_out = nullptr; s.h_out = nullptr; s.out_cap = 0;
-        RANSAC_HIP(hipMalloc((void**)&s.d_out, out_bytes));
-        RANSAC_HIP(hipHostMalloc((void**)&s.h_out, out_bytes, hipHostMallocDefault));
-        s.out_cap = out_bytes;
-    }
+    /* (the device and the pinned half of a pair are asked for the same size every time, so they grow together) */
+    MI_HIP(s.d_in.need(in_bytes));
+    MI_HIP(s.h_in.need(in_bytes));
+    MI_HIP(s.d_out.need(out_bytes));
+    MI_HIP(s.h_out.need(out_bytes));
     return 0;
 }
 
@@ -219,16 +173,20 @@ int ransac_impl(const Model& M, mi_dmrecon_ctx* ctx, const std::vector<Job>& job
     const size_t out_hyp = out_counts + align256((size_t)p.hyps * sizeof(int32_t));
     const size_t out_bytes = out_hyp + align256((size_t)p.hyps * M.hyp * sizeof(double));
 
-    RANSAC_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
-    RansacState*& state = *mi_host_ctx_ransac(ctx);
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    HostModule*& state = mi_host_ctx_module(ctx, MI_MODULE_RANSAC);
     if (!state) state = new RansacState();
-    RansacState& s = *state;
+    RansacState& s = *static_cast<RansacState*>(state);
     if (int rc = grow(s, p.in_bytes, out_bytes)) return rc;
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
+    uint8_t* const h_in = (uint8_t*)s.h_in.p;
+    uint8_t* const d_in = (uint8_t*)s.d_in.p;
+    uint8_t* const d_out = (uint8_t*)s.d_out.p;
+    const uint8_t* const h_out = (const uint8_t*)s.h_out.p;
 
-    std::memcpy(s.h_in, dev.data(), (size_t)n_jobs * sizeof(RansacJobDev));
+    std::memcpy(h_in, dev.data(), (size_t)n_jobs * sizeof(RansacJobDev));
     for (int32_t j = 0; j < n_jobs; ++j) {
-        double* list = (double*)(s.h_in + p.in_list) + (size_t)dev[j].match0 * M.entry_dev;
+        double* list = (double*)(h_in + p.in_list) + (size_t)dev[j].match0 * M.entry_dev;
         if (M.entry_in == M.entry_dev)
             std::memcpy(list, jobs[j].list, (size_t)jobs[j].n * M.entry_dev * sizeof(double));
         else
@@ -236,32 +194,32 @@ int ransac_impl(const Model& M, mi_dmrecon_ctx* ctx, const std::vector<Job>& job
                 std::memcpy(list + (size_t)i * M.entry_dev, jobs[j].list + (size_t)i * M.entry_in, M.entry_in * sizeof(double));
                 for (int k = M.entry_in; k < M.entry_dev; ++k) list[(size_t)i * M.entry_dev + k] = 0.0;
             }
-        std::memcpy(s.h_in + p.in_samples + (size_t)(dev[j].hyp0 / M.per_iteration) * M.sample * sizeof(int32_t), jobs[j].samples,
+        std::memcpy(h_in + p.in_samples + (size_t)(dev[j].hyp0 / M.per_iteration) * M.sample * sizeof(int32_t), jobs[j].samples,
                     (size_t)jobs[j].n_iterations * M.sample * sizeof(int32_t));
     }
-    RANSAC_HIP(hipMemcpyAsync(s.d_in, s.h_in, p.in_bytes, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(d_in, h_in, p.in_bytes, hipMemcpyHostToDevice, stream));
 
     RansacBuffers b;
-    b.jobs = (const RansacJobDev*)s.d_in;
-    b.list = (const double*)(s.d_in + p.in_list);
-    b.samples = (const int32_t*)(s.d_in + p.in_samples);
-    b.best_model = (double*)s.d_out;
-    b.best = (int32_t*)(s.d_out + out_best);
-    b.inliers = (int32_t*)(s.d_out + out_inliers);
-    b.counts = (int32_t*)(s.d_out + out_counts);
-    b.hyp_all = (double*)(s.d_out + out_hyp);
-    b.capped = s.d_capped;
+    b.jobs = (const RansacJobDev*)d_in;
+    b.list = (const double*)(d_in + p.in_list);
+    b.samples = (const int32_t*)(d_in + p.in_samples);
+    b.best_model = (double*)d_out;
+    b.best = (int32_t*)(d_out + out_best);
+    b.inliers = (int32_t*)(d_out + out_inliers);
+    b.counts = (int32_t*)(d_out + out_counts);
+    b.hyp_all = (double*)(d_out + out_hyp);
+    b.capped = (unsigned long long*)s.d_capped.p;
     mi_ransac_launch(stream, M.id, b, n_jobs, (int32_t)p.hyps, (int32_t)p.blocks);
-    RANSAC_HIP(hipGetLastError());
-    RANSAC_HIP(hipMemcpyAsync(s.h_out, s.d_out, per_hypothesis ? out_bytes : out_counts, hipMemcpyDeviceToHost, stream));
-    RANSAC_HIP(hipMemcpyAsync(&s.capped, s.d_capped, sizeof(s.capped), hipMemcpyDeviceToHost, stream));
-    RANSAC_HIP(hipStreamSynchronize(stream));
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipMemcpyAsync(s.h_out.p, d_out, per_hypothesis ? out_bytes : out_counts, hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipMemcpyAsync(&s.capped, s.d_capped.p, sizeof(s.capped), hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipStreamSynchronize(stream));
 
-    const double* h_model = (const double*)s.h_out;
-    const int32_t* h_best = (const int32_t*)(s.h_out + out_best);
-    const int32_t* h_inliers = (const int32_t*)(s.h_out + out_inliers);
-    const int32_t* h_counts = (const int32_t*)(s.h_out + out_counts);
-    const double* h_hyp = (const double*)(s.h_out + out_hyp);
+    const double* h_model = (const double*)h_out;
+    const int32_t* h_best = (const int32_t*)(h_out + out_best);
+    const int32_t* h_inliers = (const int32_t*)(h_out + out_inliers);
+    const int32_t* h_counts = (const int32_t*)(h_out + out_counts);
+    const double* h_hyp = (const double*)(h_out + out_hyp);
     for (int32_t j = 0; j < n_jobs; ++j) {
         if (hypothesis_counts && hypothesis_counts[j])
             std::memcpy(hypothesis_counts[j], h_counts + dev[j].hyp0, (size_t)dev[j].n_hyp * sizeof(int32_t));
@@ -280,7 +238,7 @@ int ransac_impl(const Model& M, mi_dmrecon_ctx* ctx, const std::vector<Job>& job
 template <class CJob>
 int ransac_entry(const Model& M, mi_dmrecon_ctx* ctx, int32_t n_jobs, const CJob* jobs, int32_t* best, double* model, int32_t* n_inliers,
                  int32_t* const* inliers, int32_t* const* counts, double* const* all) {
-    try {
+    return guarded([&] {
         if (!ctx) return failf(MI_DMRECON_EINVAL, "ransac: null context");
         if (n_jobs < 0) return failf(MI_DMRECON_EINVAL, "ransac: negative number of jobs");
         if (n_jobs > 0 && !jobs) return failf(MI_DMRECON_EINVAL, "ransac: null argument");
@@ -288,8 +246,7 @@ int ransac_entry(const Model& M, mi_dmrecon_ctx* ctx, int32_t n_jobs, const CJob
         list.reserve(n_jobs);
         for (int32_t j = 0; j < n_jobs; ++j) list.push_back(job_of(jobs[j]));
         return ransac_impl(M, ctx, list, best, model, n_inliers, inliers, counts, all);
-    }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    });
 }
 
 }  /* namespace */
@@ -315,7 +272,7 @@ int mi_dmrecon_ransac_pose_three_point(mi_dmrecon_ctx* ctx, int32_t n_jobs, cons
 }
 
 long long mi_dmrecon_ransac_sweep_capped(mi_dmrecon_ctx* ctx) {
-    RansacState* s = ctx ? *mi_host_ctx_ransac(ctx) : nullptr;
+    const RansacState* s = ctx ? static_cast<RansacState*>(mi_host_ctx_module(ctx, MI_MODULE_RANSAC)) : nullptr;
     return s ? (long long)s->capped : 0;
 }
 

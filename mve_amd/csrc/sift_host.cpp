@@ -14,73 +14,20 @@
 #include <new>
 #include <vector>
 
-#include "../../include/mi_dmrecon.h"
+#include "host_common.h"
 #include "sift_device.h"
 
-/* dmrecon_host.cpp (not exported, exports.map) */
-struct SiftState;
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
-SiftState** mi_host_ctx_sift(mi_dmrecon_ctx* c);
-
 namespace {
 
-/* device (or pinned host) memory that only grows */
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool host = false;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        hipError_t e = host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes; else p = nullptr;
-        return e;
-    }
-    void release() {
-        if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-        p = nullptr; cap = 0;
-    }
-};
-
-}  /* namespace */
-
-struct SiftState {
-    Buf h_pix, d_pix, d_orig, d_pp[2], d_tmp, d_img, d_dog, d_masks, d_words, d_cand, d_loc, d_block, d_kp, d_ori, d_nori, d_xyso, d_desc,
-        d_counts, h_counts;
+struct SiftState : HostModule {
+    PinnedBuf h_pix, h_counts;
+    Buf d_pix, d_orig, d_pp[2], d_tmp, d_img, d_dog, d_masks, d_words, d_cand, d_loc, d_block, d_kp, d_ori, d_nori, d_xyso, d_desc, d_counts;
     int32_t cand_cap = 1 << 18, kp_cap = 1 << 16, desc_cap = 1 << 16;
     int32_t n_kp = -1, n_desc = -1;          /* of the last run; -1: there was none, or it failed */
-    SiftState() { h_pix.host = true; h_counts.host = true; }
 };
-
-void mi_sift_release(SiftState* s) {
-    if (!s) return;
-    Buf* all[] = {&s->h_pix, &s->d_pix, &s->d_orig, &s->d_pp[0], &s->d_pp[1], &s->d_tmp, &s->d_img, &s->d_dog, &s->d_masks, &s->d_words,
-                  &s->d_cand, &s->d_loc, &s->d_block, &s->d_kp, &s->d_ori, &s->d_nori, &s->d_xyso, &s->d_desc, &s->d_counts, &s->h_counts};
-    for (Buf* b : all) b->release();
-    delete s;
-}
-
-namespace {
 
 #define SIFT_MAX_SIDE 32767                  /* a candidate is x | y << 16 */
 #define SIFT_MAX_PIXELS (1ll << 28)          /* of the largest octave image */
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0, long long c = 0, long long d = 0) {
-    char buf[320];
-    std::snprintf(buf, sizeof(buf), fmt, a, b, c, d);
-    return mi_host_fail(code, buf);
-}
-
-#define SIFT_HIP(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
 
 /* One octave of the plan: its size, where its source comes from and the S + 3 blurs (the first one brings the source to
  * base_blur_sigma, sift.cc:221-226; ks = 0 stands for a copy). */
@@ -190,10 +137,10 @@ int sift_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const
         if (bad >= 0) return failf(MI_DMRECON_EINVAL, "sift: pixels: value %lld is not finite", bad);
     }
 
-    SIFT_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
-    SiftState*& state = *mi_host_ctx_sift(ctx);
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    HostModule*& state = mi_host_ctx_module(ctx, MI_MODULE_SIFT);
     if (!state) state = new SiftState();
-    SiftState& s = *state;
+    SiftState& s = *static_cast<SiftState*>(state);
     s.n_kp = s.n_desc = -1;
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
     const int S = o.num_samples_per_octave;
@@ -203,32 +150,32 @@ int sift_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const
         max_words = std::max(max_words, (size_t)S * p.h * ((p.w + 63) / 64));
     }
     const size_t in_bytes = n_values * (is_float ? sizeof(float) : 1);
-    SIFT_HIP(s.h_pix.need(in_bytes));
-    SIFT_HIP(s.d_pix.need(in_bytes));
-    SIFT_HIP(s.d_orig.need((size_t)w * h * sizeof(float)));
-    SIFT_HIP(s.d_pp[0].need(max_px * sizeof(float)));
-    SIFT_HIP(s.d_pp[1].need(max_px * sizeof(float)));
-    SIFT_HIP(s.d_tmp.need(max_px * sizeof(float)));
-    SIFT_HIP(s.d_img.need(max_px * (S + 3) * sizeof(float)));
-    SIFT_HIP(s.d_dog.need(max_px * (S + 2) * sizeof(float)));
-    SIFT_HIP(s.d_masks.need(max_words * sizeof(unsigned long long)));
-    SIFT_HIP(s.d_words.need(max_words * sizeof(int32_t)));
-    SIFT_HIP(s.d_counts.need(sizeof(SiftCounts)));
-    SIFT_HIP(s.h_counts.need(sizeof(SiftCounts)));
+    MI_HIP(s.h_pix.need(in_bytes));
+    MI_HIP(s.d_pix.need(in_bytes));
+    MI_HIP(s.d_orig.need((size_t)w * h * sizeof(float)));
+    MI_HIP(s.d_pp[0].need(max_px * sizeof(float)));
+    MI_HIP(s.d_pp[1].need(max_px * sizeof(float)));
+    MI_HIP(s.d_tmp.need(max_px * sizeof(float)));
+    MI_HIP(s.d_img.need(max_px * (S + 3) * sizeof(float)));
+    MI_HIP(s.d_dog.need(max_px * (S + 2) * sizeof(float)));
+    MI_HIP(s.d_masks.need(max_words * sizeof(unsigned long long)));
+    MI_HIP(s.d_words.need(max_words * sizeof(int32_t)));
+    MI_HIP(s.d_counts.need(sizeof(SiftCounts)));
+    MI_HIP(s.h_counts.need(sizeof(SiftCounts)));
     std::memcpy(s.h_pix.p, pixels, in_bytes);
 
     for (int attempt = 0; attempt < 8; ++attempt) {
-        SIFT_HIP(s.d_cand.need((size_t)s.cand_cap * sizeof(int2)));
-        SIFT_HIP(s.d_loc.need((size_t)s.cand_cap * sizeof(float4)));
-        SIFT_HIP(s.d_block.need((size_t)((s.cand_cap + 255) / 256) * sizeof(int32_t)));
-        SIFT_HIP(s.d_kp.need((size_t)s.kp_cap * sizeof(SiftKeypoint)));
-        SIFT_HIP(s.d_ori.need((size_t)s.kp_cap * SIFT_MAX_ORI * sizeof(float)));
-        SIFT_HIP(s.d_nori.need((size_t)s.kp_cap * sizeof(int32_t)));
-        SIFT_HIP(s.d_xyso.need((size_t)s.desc_cap * 4 * sizeof(float)));
-        SIFT_HIP(s.d_desc.need((size_t)s.desc_cap * 128 * sizeof(float)));
+        MI_HIP(s.d_cand.need((size_t)s.cand_cap * sizeof(int2)));
+        MI_HIP(s.d_loc.need((size_t)s.cand_cap * sizeof(float4)));
+        MI_HIP(s.d_block.need((size_t)((s.cand_cap + 255) / 256) * sizeof(int32_t)));
+        MI_HIP(s.d_kp.need((size_t)s.kp_cap * sizeof(SiftKeypoint)));
+        MI_HIP(s.d_ori.need((size_t)s.kp_cap * SIFT_MAX_ORI * sizeof(float)));
+        MI_HIP(s.d_nori.need((size_t)s.kp_cap * sizeof(int32_t)));
+        MI_HIP(s.d_xyso.need((size_t)s.desc_cap * 4 * sizeof(float)));
+        MI_HIP(s.d_desc.need((size_t)s.desc_cap * 128 * sizeof(float)));
 
         if (attempt == 0) {
-            SIFT_HIP(hipMemcpyAsync(s.d_pix.p, s.h_pix.p, in_bytes, hipMemcpyHostToDevice, stream));
+            MI_HIP(hipMemcpyAsync(s.d_pix.p, s.h_pix.p, in_bytes, hipMemcpyHostToDevice, stream));
             mi_sift_gray(stream, s.d_pix.p, is_float, channels, (float*)s.d_orig.p, (long long)w * h);
         }
         const float* cur = (const float*)s.d_orig.p;
@@ -261,9 +208,9 @@ int sift_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const
             a.xyso = (float*)s.d_xyso.p; a.desc = (float*)s.d_desc.p; a.desc_cap = s.desc_cap; a.counts = (SiftCounts*)s.d_counts.p;
             mi_sift_detect_describe(stream, a);
         }
-        SIFT_HIP(hipGetLastError());
-        SIFT_HIP(hipMemcpyAsync(s.h_counts.p, s.d_counts.p, sizeof(SiftCounts), hipMemcpyDeviceToHost, stream));
-        SIFT_HIP(hipStreamSynchronize(stream));
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipMemcpyAsync(s.h_counts.p, s.d_counts.p, sizeof(SiftCounts), hipMemcpyDeviceToHost, stream));
+        MI_HIP(hipStreamSynchronize(stream));
         const SiftCounts& c = *(const SiftCounts*)s.h_counts.p;
         long long max_cand = 0, n_kp = 0, n_desc = 0;
         for (size_t k = 0; k < plan.size(); ++k) {
@@ -287,15 +234,15 @@ int sift_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const
 
 int sift_get_impl(mi_dmrecon_ctx* ctx, mi_dmrecon_sift_keypoint* kp, float* xyso, float* desc) {
     if (!ctx) return failf(MI_DMRECON_EINVAL, "sift: null context");
-    SiftState* s = *mi_host_ctx_sift(ctx);
+    const SiftState* s = static_cast<SiftState*>(mi_host_ctx_module(ctx, MI_MODULE_SIFT));
     if (!s || s->n_kp < 0) return failf(MI_DMRECON_EINVAL, "sift: mi_dmrecon_sift_get without a successful mi_dmrecon_sift_run on this context");
-    SIFT_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
     static_assert(sizeof(mi_dmrecon_sift_keypoint) == sizeof(SiftKeypoint), "the kernels write the public keypoint");
-    if (kp && s->n_kp) SIFT_HIP(hipMemcpyAsync(kp, s->d_kp.p, (size_t)s->n_kp * sizeof(SiftKeypoint), hipMemcpyDeviceToHost, stream));
-    if (xyso && s->n_desc) SIFT_HIP(hipMemcpyAsync(xyso, s->d_xyso.p, (size_t)s->n_desc * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (desc && s->n_desc) SIFT_HIP(hipMemcpyAsync(desc, s->d_desc.p, (size_t)s->n_desc * 128 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    SIFT_HIP(hipStreamSynchronize(stream));
+    if (kp && s->n_kp) MI_HIP(hipMemcpyAsync(kp, s->d_kp.p, (size_t)s->n_kp * sizeof(SiftKeypoint), hipMemcpyDeviceToHost, stream));
+    if (xyso && s->n_desc) MI_HIP(hipMemcpyAsync(xyso, s->d_xyso.p, (size_t)s->n_desc * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (desc && s->n_desc) MI_HIP(hipMemcpyAsync(desc, s->d_desc.p, (size_t)s->n_desc * 128 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -305,8 +252,7 @@ extern "C" {
 
 int mi_dmrecon_sift_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const void* pixels, int32_t is_float, int32_t w, int32_t h,
                         int32_t channels, int32_t* n_keypoints, int32_t* n_descriptors) {
-    try { return sift_run_impl(ctx, opt, pixels, is_float, w, h, channels, n_keypoints, n_descriptors); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return sift_run_impl(ctx, opt, pixels, is_float, w, h, channels, n_keypoints, n_descriptors); });
 }
 
 int mi_dmrecon_sift_get(mi_dmrecon_ctx* ctx, mi_dmrecon_sift_keypoint* kp, float* xyso, float* desc) {

@@ -14,73 +14,21 @@
 #include <cstring>
 #include <new>
 
-#include "../../include/mi_dmrecon.h"
+#include "host_common.h"
 #include "surf_device.h"
-
-/* dmrecon_host.cpp (not exported, exports.map) */
-struct SurfState;
-int mi_host_fail(int code, const char* msg);
-int mi_host_ctx_device(const mi_dmrecon_ctx* c);
-SurfState** mi_host_ctx_surf(mi_dmrecon_ctx* c);
 
 namespace {
 
-/* device (or pinned host) memory that only grows */
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool host = false;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        hipError_t e = host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes; else p = nullptr;
-        return e;
-    }
-    void release() {
-        if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-        p = nullptr; cap = 0;
-    }
-};
-
-}  /* namespace */
-
-struct SurfState {
-    Buf h_pix, d_pix, d_sat, d_maps, d_words, d_kp, d_ori, d_stage, d_slot, d_tmp, d_xyso, d_desc, h_tab, d_tab, d_counts, h_counts;
+struct SurfState : HostModule {
+    PinnedBuf h_pix, h_tab, h_counts;
+    Buf d_pix, d_sat, d_maps, d_words, d_kp, d_ori, d_stage, d_slot, d_tmp, d_xyso, d_desc, d_tab, d_counts;
     bool tables_up = false;
     int32_t kp_cap = 1 << 15;
     int32_t n_kp = -1, n_desc = -1;          /* of the last run; -1: there was none, or it failed */
-    SurfState() { h_pix.host = true; h_tab.host = true; h_counts.host = true; }
 };
-
-void mi_surf_release(SurfState* s) {
-    if (!s) return;
-    Buf* all[] = {&s->h_pix, &s->d_pix, &s->d_sat, &s->d_maps, &s->d_words, &s->d_kp, &s->d_ori, &s->d_stage, &s->d_slot, &s->d_tmp,
-                  &s->d_xyso, &s->d_desc, &s->h_tab, &s->d_tab, &s->d_counts, &s->h_counts};
-    for (Buf* b : all) b->release();
-    delete s;
-}
-
-namespace {
 
 #define SURF_MAX_SIDE 32767
 #define SURF_MAX_PIXELS (1ll << 28)
-
-int failf(int code, const char* fmt, long long a = 0, long long b = 0, long long c = 0) {
-    char buf[320];
-    std::snprintf(buf, sizeof(buf), fmt, a, b, c);
-    return mi_host_fail(code, buf);
-}
-
-#define SURF_HIP(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            char _b[256];                                                                     \
-            std::snprintf(_b, sizeof(_b), "%s failed: %s", #expr, hipGetErrorString(_e));     \
-            return mi_host_fail(MI_DMRECON_EDEVICE, _b);                                      \
-        }                                                                                     \
-    } while (0)
 
 void make_tables(SurfTables* t) {
     std::memset(t, 0, sizeof(*t));
@@ -119,10 +67,10 @@ int surf_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const
         return failf(MI_DMRECON_EINVAL, "surf: w, h: a %lld x %lld image; 1 ... %lld a side and 2^28 pixels expected", w, h, SURF_MAX_SIDE);
     if (!std::isfinite(opt->contrast_threshold)) return failf(MI_DMRECON_EINVAL, "surf: contrast_threshold is not finite");
 
-    SURF_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
-    SurfState*& state = *mi_host_ctx_surf(ctx);
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    HostModule*& state = mi_host_ctx_module(ctx, MI_MODULE_SURF);
     if (!state) state = new SurfState();
-    SurfState& s = *state;
+    SurfState& s = *static_cast<SurfState*>(state);
     s.n_kp = s.n_desc = -1;
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
 
@@ -139,20 +87,20 @@ int surf_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const
     }
     a.n_words = (int32_t)n_words;
     const size_t in_bytes = (size_t)w * h * channels;
-    SURF_HIP(s.h_pix.need(in_bytes));
-    SURF_HIP(s.d_pix.need(in_bytes));
-    SURF_HIP(s.d_sat.need((size_t)w * h * sizeof(uint32_t)));
-    SURF_HIP(s.d_maps.need((size_t)n_maps * sizeof(float)));
-    SURF_HIP(s.d_words.need((size_t)n_words * sizeof(int32_t)));
-    SURF_HIP(s.h_tab.need(sizeof(SurfTables)));
-    SURF_HIP(s.d_tab.need(sizeof(SurfTables)));
-    SURF_HIP(s.d_counts.need(sizeof(SurfCounts)));
-    SURF_HIP(s.h_counts.need(sizeof(SurfCounts)));
+    MI_HIP(s.h_pix.need(in_bytes));
+    MI_HIP(s.d_pix.need(in_bytes));
+    MI_HIP(s.d_sat.need((size_t)w * h * sizeof(uint32_t)));
+    MI_HIP(s.d_maps.need((size_t)n_maps * sizeof(float)));
+    MI_HIP(s.d_words.need((size_t)n_words * sizeof(int32_t)));
+    MI_HIP(s.h_tab.need(sizeof(SurfTables)));
+    MI_HIP(s.d_tab.need(sizeof(SurfTables)));
+    MI_HIP(s.d_counts.need(sizeof(SurfCounts)));
+    MI_HIP(s.h_counts.need(sizeof(SurfCounts)));
     std::memcpy(s.h_pix.p, pixels, in_bytes);
-    SURF_HIP(hipMemcpyAsync(s.d_pix.p, s.h_pix.p, in_bytes, hipMemcpyHostToDevice, stream));
+    MI_HIP(hipMemcpyAsync(s.d_pix.p, s.h_pix.p, in_bytes, hipMemcpyHostToDevice, stream));
     if (!s.tables_up) {
         make_tables((SurfTables*)s.h_tab.p);
-        SURF_HIP(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, sizeof(SurfTables), hipMemcpyHostToDevice, stream));
+        MI_HIP(hipMemcpyAsync(s.d_tab.p, s.h_tab.p, sizeof(SurfTables), hipMemcpyHostToDevice, stream));
         s.tables_up = true;
     }
     a.pixels = (const unsigned char*)s.d_pix.p; a.sat = (uint32_t*)s.d_sat.p; a.maps = (float*)s.d_maps.p; a.words = (int32_t*)s.d_words.p;
@@ -162,20 +110,20 @@ int surf_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const
 
     for (int attempt = 0; attempt < 4; ++attempt) {
         const size_t cap = (size_t)s.kp_cap;
-        SURF_HIP(s.d_kp.need(cap * sizeof(SurfKeypoint)));
-        SURF_HIP(s.d_ori.need(cap * sizeof(float)));
-        SURF_HIP(s.d_stage.need(cap * sizeof(int32_t)));
-        SURF_HIP(s.d_slot.need(cap * sizeof(int32_t)));
-        SURF_HIP(s.d_tmp.need(cap * 64 * sizeof(float)));
-        SURF_HIP(s.d_xyso.need(cap * 4 * sizeof(float)));
-        SURF_HIP(s.d_desc.need(cap * 64 * sizeof(float)));
+        MI_HIP(s.d_kp.need(cap * sizeof(SurfKeypoint)));
+        MI_HIP(s.d_ori.need(cap * sizeof(float)));
+        MI_HIP(s.d_stage.need(cap * sizeof(int32_t)));
+        MI_HIP(s.d_slot.need(cap * sizeof(int32_t)));
+        MI_HIP(s.d_tmp.need(cap * 64 * sizeof(float)));
+        MI_HIP(s.d_xyso.need(cap * 4 * sizeof(float)));
+        MI_HIP(s.d_desc.need(cap * 64 * sizeof(float)));
         a.kp = (SurfKeypoint*)s.d_kp.p; a.kp_cap = s.kp_cap; a.ori = (float*)s.d_ori.p; a.stage = (int32_t*)s.d_stage.p;
         a.slot = (int32_t*)s.d_slot.p; a.tmp_desc = (float*)s.d_tmp.p; a.xyso = (float*)s.d_xyso.p; a.desc = (float*)s.d_desc.p;
         mi_surf_detect(stream, a);
         mi_surf_describe(stream, a);
-        SURF_HIP(hipGetLastError());
-        SURF_HIP(hipMemcpyAsync(s.h_counts.p, s.d_counts.p, sizeof(SurfCounts), hipMemcpyDeviceToHost, stream));
-        SURF_HIP(hipStreamSynchronize(stream));
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipMemcpyAsync(s.h_counts.p, s.d_counts.p, sizeof(SurfCounts), hipMemcpyDeviceToHost, stream));
+        MI_HIP(hipStreamSynchronize(stream));
         const SurfCounts c = *(const SurfCounts*)s.h_counts.p;
         if (c.n_kp <= s.kp_cap) {
             s.n_kp = c.n_kp; s.n_desc = c.n_desc;
@@ -191,15 +139,15 @@ int surf_run_impl(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const
 
 int surf_get_impl(mi_dmrecon_ctx* ctx, mi_dmrecon_surf_keypoint* kp, float* xyso, float* desc) {
     if (!ctx) return failf(MI_DMRECON_EINVAL, "surf: null context");
-    SurfState* s = *mi_host_ctx_surf(ctx);
+    const SurfState* s = static_cast<SurfState*>(mi_host_ctx_module(ctx, MI_MODULE_SURF));
     if (!s || s->n_kp < 0) return failf(MI_DMRECON_EINVAL, "surf: mi_dmrecon_surf_get without a successful mi_dmrecon_surf_run on this context");
-    SURF_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
+    MI_HIP(hipSetDevice(mi_host_ctx_device(ctx)));
     hipStream_t stream = (hipStream_t)mi_dmrecon_ctx_stream(ctx);
     static_assert(sizeof(mi_dmrecon_surf_keypoint) == sizeof(SurfKeypoint), "the kernels write the public keypoint");
-    if (kp && s->n_kp) SURF_HIP(hipMemcpyAsync(kp, s->d_kp.p, (size_t)s->n_kp * sizeof(SurfKeypoint), hipMemcpyDeviceToHost, stream));
-    if (xyso && s->n_desc) SURF_HIP(hipMemcpyAsync(xyso, s->d_xyso.p, (size_t)s->n_desc * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (desc && s->n_desc) SURF_HIP(hipMemcpyAsync(desc, s->d_desc.p, (size_t)s->n_desc * 64 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    SURF_HIP(hipStreamSynchronize(stream));
+    if (kp && s->n_kp) MI_HIP(hipMemcpyAsync(kp, s->d_kp.p, (size_t)s->n_kp * sizeof(SurfKeypoint), hipMemcpyDeviceToHost, stream));
+    if (xyso && s->n_desc) MI_HIP(hipMemcpyAsync(xyso, s->d_xyso.p, (size_t)s->n_desc * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (desc && s->n_desc) MI_HIP(hipMemcpyAsync(desc, s->d_desc.p, (size_t)s->n_desc * 64 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    MI_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -209,8 +157,7 @@ extern "C" {
 
 int mi_dmrecon_surf_run(mi_dmrecon_ctx* ctx, const mi_dmrecon_surf_options* opt, const uint8_t* pixels, int32_t w, int32_t h,
                         int32_t channels, int32_t* n_keypoints, int32_t* n_descriptors) {
-    try { return surf_run_impl(ctx, opt, pixels, w, h, channels, n_keypoints, n_descriptors); }
-    catch (const std::bad_alloc&) { return mi_host_fail(MI_DMRECON_EDEVICE, "out of host memory"); }
+    return guarded([&] { return surf_run_impl(ctx, opt, pixels, w, h, channels, n_keypoints, n_descriptors); });
 }
 
 int mi_dmrecon_surf_get(mi_dmrecon_ctx* ctx, mi_dmrecon_surf_keypoint* kp, float* xyso, float* desc) {

@@ -10,7 +10,7 @@
  *   :43-66  the voxels are the unique VoxelIndex set of all leaf corners, in ascending index order,
  *   :68-69  "Sampling the implicit function at N positions, fetch a beer...",
  *   :215-250 the progress line (between the chunks the GPU works through, and once at 100 %).
- * Device choice: the first entry of MI_DMRECON_DEVICES (default 0), as the dmrecon shim reads it.
+ * A context of its own per sampling, on the first entry of MI_DMRECON_DEVICES (default 0; shim_common.h).
  */
 #include <algorithm>
 #include <cstdint>
@@ -26,37 +26,13 @@
 #include "util/timer.h"
 #include "fssr/iso_octree.h"
 
-#include "mi_dmrecon.h"
+#include "shim_common.h"
 
 FSSR_NAMESPACE_BEGIN
 
 namespace {
 
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("fssr::IsoOctree (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
+using mi_shim::check;
 
 /* The tree as include/mi_dmrecon.h wants it: nodes breadth first (the eight children of a node consecutive and after it),
  * samples in the order Octree::influence_query visits them (a node's own, then its subtrees 0..7). */
@@ -158,7 +134,7 @@ IsoOctree::compute_all_voxels (void)
     flatten(*this, &flat);
 
     mi_dmrecon_ctx* ctx = nullptr;
-    check(mi_dmrecon_ctx_create(first_device(), &ctx), "mi_dmrecon_ctx_create");
+    check(mi_dmrecon_ctx_create(mi_shim::first_device("fssr::IsoOctree"), &ctx), "mi_dmrecon_ctx_create");
     mi_dmrecon_fssr* handle = nullptr;
     math::Vec3d const center = this->get_root_node_center();
     double const root_center[3] = { center[0], center[1], center[2] };

@@ -13,8 +13,9 @@
  * reference's to rounding and to where its CG stops, not bit for bit (include/mi_dmrecon.h).  The private helpers have no
  * other caller in the reference and throw std::logic_error.
  *
- * One context for the process, made by the first call on the first entry of MI_DMRECON_DEVICES (default 0), as the other
- * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit.
+ * One context for the process, shared with every other drop-in of this directory that the binary links (shim_common.h): made
+ * by the first call of any of them on the first entry of MI_DMRECON_DEVICES (default 0); every calling thread works on its
+ * own fork (its own stream and buffers); all are released at exit.
  */
 #include <algorithm>
 #include <cstdint>
@@ -30,72 +31,12 @@
 #include "util/timer.h"
 #include "sfm/bundle_adjustment.h"
 
-#include "mi_dmrecon.h"
+#include "shim_common.h"
 
 #define LOG_V this->log.verbose()
 
 SFM_NAMESPACE_BEGIN
 SFM_BA_NAMESPACE_BEGIN
-
-namespace {
-
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("sfm::ba::BundleAdjustment (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
-
-/* the process-wide context and its forks */
-struct Contexts
-{
-    std::mutex mutex;
-    mi_dmrecon_ctx* parent = nullptr;
-    std::vector<mi_dmrecon_ctx*> forks;
-    ~Contexts (void)
-    {
-        for (std::size_t i = 0; i < this->forks.size(); ++i)
-            mi_dmrecon_ctx_destroy(this->forks[i]);
-        if (this->parent != nullptr)
-            mi_dmrecon_ctx_destroy(this->parent);
-    }
-};
-
-Contexts contexts;
-
-mi_dmrecon_ctx* context_of_this_thread(void)
-{
-    static thread_local mi_dmrecon_ctx* mine = nullptr;
-    if (mine != nullptr)
-        return mine;
-    std::lock_guard<std::mutex> lock(contexts.mutex);
-    if (contexts.parent == nullptr)
-        check(mi_dmrecon_ctx_create(first_device(), &contexts.parent), "mi_dmrecon_ctx_create");
-    check(mi_dmrecon_ctx_fork(contexts.parent, &mine), "mi_dmrecon_ctx_fork");
-    contexts.forks.push_back(mine);
-    return mine;
-}
-
-}  /* namespace */
 
 BundleAdjustment::Status
 BundleAdjustment::optimize (void)
@@ -168,7 +109,7 @@ BundleAdjustment::lm_optimize (void)
     int const capacity = std::max(o.lm_max_iterations, o.lm_min_iterations);
     std::vector<mi_dmrecon_ba_trace> trace(capacity);
     mi_dmrecon_ba_status st;
-    check(mi_dmrecon_ba_optimize(context_of_this_thread(), &o, static_cast<int32_t>(cams.size()), cams.data(),
+    mi_shim::check(mi_dmrecon_ba_optimize(mi_shim::context_of_this_thread("sfm::ba::BundleAdjustment"), &o, static_cast<int32_t>(cams.size()), cams.data(),
         static_cast<int32_t>(pts.size()), pts.data(), static_cast<int32_t>(this->observations->size()),
         reinterpret_cast<mi_dmrecon_ba_observation const*>(this->observations->data()), &st, trace.data(), capacity),
         "mi_dmrecon_ba_optimize");

@@ -15,7 +15,7 @@
  *
  * The class has no spare member and a defaulted destructor, so the matcher handle of an object lives in a registry keyed
  * by `this`: replaced by the next init of the same object, released at process exit.
- * Device choice: the first entry of MI_DMRECON_DEVICES (default 0), as the dmrecon shim reads it.
+ * A context of its own per object, on the first entry of MI_DMRECON_DEVICES (default 0; shim_common.h).
  */
 #include <algorithm>
 #include <cstdint>
@@ -30,37 +30,13 @@
 
 #include "sfm/exhaustive_matching.h"
 
-#include "mi_dmrecon.h"
+#include "shim_common.h"
 
 SFM_NAMESPACE_BEGIN
 
 namespace {
 
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("sfm::ExhaustiveMatching (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
+using mi_shim::check;
 
 /* the context and the matcher of one ExhaustiveMatching object */
 struct Device
@@ -124,7 +100,7 @@ ExhaustiveMatching::init (bundler::ViewportList* viewports)
 
     /* the discretised sets, as the class holds them, onto the device */
     std::shared_ptr<Device> dev(new Device());
-    check(mi_dmrecon_ctx_create(first_device(), &dev->ctx), "mi_dmrecon_ctx_create");
+    check(mi_dmrecon_ctx_create(mi_shim::first_device("sfm::ExhaustiveMatching"), &dev->ctx), "mi_dmrecon_ctx_create");
     check(mi_dmrecon_match_create(dev->ctx, static_cast<int32_t>(viewports->size()), &dev->match), "mi_dmrecon_match_create");
     for (std::size_t i = 0; i < viewports->size(); ++i)
     {

@@ -16,9 +16,9 @@
  * What differs: the 8-point solves and the Sampson tests of all iterations run on the GPU (mi_dmrecon_ransac_fundamental);
  * F and the inlier set agree with the reference's to rounding, not bit for bit (include/mi_dmrecon.h).
  *
- * One context for the process, made by the first call on the first entry of MI_DMRECON_DEVICES (default 0), as the other
- * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit
- * (ransac_shim.h, shared with the homography and P3P drop-ins).
+ * One context for the process, shared with every other drop-in of this directory that the binary links (shim_common.h): made
+ * by the first call of any of them on the first entry of MI_DMRECON_DEVICES (default 0); every calling thread works on its
+ * own fork (its own stream and buffers); all are released at exit.
  */
 #include <cstdint>
 #include <iostream>
@@ -68,7 +68,7 @@ RansacFundamental::estimate (Correspondences2D2D const& matches, Result* result)
     std::vector<int32_t> counts(this->opts.verbose_output ? this->opts.max_iterations : 0);
     int32_t* inliers_ptr = inliers.data();
     int32_t* counts_ptr = counts.data();
-    mi_ransac_shim::check(mi_dmrecon_ransac_fundamental(mi_ransac_shim::context_of_this_thread("sfm::RansacFundamental"), 1, &job, &best_iteration, fundamental, &n_inliers,
+    mi_shim::check(mi_dmrecon_ransac_fundamental(mi_shim::context_of_this_thread("sfm::RansacFundamental"), 1, &job, &best_iteration, fundamental, &n_inliers,
         &inliers_ptr, this->opts.verbose_output ? &counts_ptr : nullptr, nullptr), "mi_dmrecon_ransac_fundamental");
 
     if (this->opts.verbose_output)

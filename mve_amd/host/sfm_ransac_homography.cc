@@ -13,7 +13,7 @@
  *   :44, :54-55  result is written only by an iteration with MORE inliers than result->inliers holds on entry.
  * What differs: the DLT solves and the symmetric transfer errors of all iterations run on the GPU
  * (mi_dmrecon_ransac_homography); H and the inlier set agree with the reference's to rounding, not bit for bit
- * (include/mi_dmrecon.h).  The context and its forks: ransac_shim.h.
+ * (include/mi_dmrecon.h).  The context and its forks: shim_common.h.
  */
 #include <cstdint>
 #include <iostream>
@@ -63,7 +63,7 @@ RansacHomography::estimate (Correspondences2D2D const& matches, Result* result)
     std::vector<int32_t> counts(this->opts.verbose_output ? this->opts.max_iterations : 0);
     int32_t* inliers_ptr = inliers.data();
     int32_t* counts_ptr = counts.data();
-    mi_ransac_shim::check(mi_dmrecon_ransac_homography(mi_ransac_shim::context_of_this_thread("sfm::RansacHomography"), 1,
+    mi_shim::check(mi_dmrecon_ransac_homography(mi_shim::context_of_this_thread("sfm::RansacHomography"), 1,
         &job, &best_iteration, homography, &n_inliers, &inliers_ptr, this->opts.verbose_output ? &counts_ptr : nullptr,
         nullptr), "mi_dmrecon_ransac_homography");
 

@@ -16,7 +16,7 @@
  * The reference's loop is an OpenMP loop (:41-46): which thread draws which sample, and which of two poses with equally
  * many inliers reaches the critical section first, depend on the thread schedule.  This shim reproduces the SINGLE-THREAD
  * order: iteration i uses the i-th draws, and the winner is the first hypothesis 4 * iteration + root with the most inliers.
- * The context and its forks: ransac_shim.h.
+ * The context and its forks: shim_common.h.
  */
 #include <cstdint>
 #include <iostream>
@@ -69,7 +69,7 @@ RansacPoseP3P::estimate (Correspondences2D3D const& corresp,
     std::vector<int32_t> counts(this->opts.verbose_output ? 4 * static_cast<std::size_t>(this->opts.max_iterations) : 0);
     int32_t* inliers_ptr = inliers.data();
     int32_t* counts_ptr = counts.data();
-    mi_ransac_shim::check(mi_dmrecon_ransac_pose_three_point(mi_ransac_shim::context_of_this_thread("sfm::RansacPoseP3P"), 1, &job,
+    mi_shim::check(mi_dmrecon_ransac_pose_three_point(mi_shim::context_of_this_thread("sfm::RansacPoseP3P"), 1, &job,
         &best_hypothesis, pose, &n_inliers, &inliers_ptr, this->opts.verbose_output ? &counts_ptr : nullptr, nullptr),
         "mi_dmrecon_ransac_pose_three_point");
 

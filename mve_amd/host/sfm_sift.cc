@@ -16,8 +16,9 @@
  * reference's to rounding, not bit for bit (include/mi_dmrecon.h).  The protected stage members have no other caller and
  * throw std::logic_error.
  *
- * One context for the process, made by the first call on the first entry of MI_DMRECON_DEVICES (default 0), as the other
- * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit.
+ * One context for the process, shared with every other drop-in of this directory that the binary links (shim_common.h): made
+ * by the first call of any of them on the first entry of MI_DMRECON_DEVICES (default 0); every calling thread works on its
+ * own fork (its own stream and buffers); all are released at exit.
  */
 #include <cstdint>
 #include <cstdlib>
@@ -34,69 +35,11 @@
 #include "mve/image.h"
 #include "sfm/sift.h"
 
-#include "mi_dmrecon.h"
+#include "shim_common.h"
 
 SFM_NAMESPACE_BEGIN
 
 namespace {
-
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("sfm::Sift (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc == MI_DMRECON_EINVAL)
-        throw std::invalid_argument(mi_dmrecon_last_error());
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
-
-/* the process-wide context and its forks */
-struct Contexts
-{
-    std::mutex mutex;
-    mi_dmrecon_ctx* parent = nullptr;
-    std::vector<mi_dmrecon_ctx*> forks;
-    ~Contexts (void)
-    {
-        for (std::size_t i = 0; i < this->forks.size(); ++i)
-            mi_dmrecon_ctx_destroy(this->forks[i]);
-        if (this->parent != nullptr)
-            mi_dmrecon_ctx_destroy(this->parent);
-    }
-};
-
-Contexts contexts;
-
-mi_dmrecon_ctx* context_of_this_thread(void)
-{
-    static thread_local mi_dmrecon_ctx* mine = nullptr;
-    if (mine != nullptr)
-        return mine;
-    std::lock_guard<std::mutex> lock(contexts.mutex);
-    if (contexts.parent == nullptr)
-        check(mi_dmrecon_ctx_create(first_device(), &contexts.parent), "mi_dmrecon_ctx_create");
-    check(mi_dmrecon_ctx_fork(contexts.parent, &mine), "mi_dmrecon_ctx_fork");
-    contexts.forks.push_back(mine);
-    return mine;
-}
 
 /* one grey float channel: a byte is value / 255 clamped to [0, 1], a colour is the mean of its three channels */
 template <typename T>
@@ -169,13 +112,13 @@ Sift::process (void)
     opt.base_blur_sigma = this->options.base_blur_sigma;
     opt.inherent_blur_sigma = this->options.inherent_blur_sigma;
 
-    mi_dmrecon_ctx* ctx = context_of_this_thread();
+    mi_dmrecon_ctx* ctx = mi_shim::context_of_this_thread("sfm::Sift");
     int32_t n_keypoints = 0, n_descriptors = 0;
-    check(mi_dmrecon_sift_run(ctx, &opt, this->orig->begin(), 1, this->orig->width(), this->orig->height(), 1,
+    mi_shim::check_args(mi_dmrecon_sift_run(ctx, &opt, this->orig->begin(), 1, this->orig->width(), this->orig->height(), 1,
         &n_keypoints, &n_descriptors), "mi_dmrecon_sift_run");
     std::vector<mi_dmrecon_sift_keypoint> kp(n_keypoints);
     std::vector<float> xyso(static_cast<std::size_t>(n_descriptors) * 4), data(static_cast<std::size_t>(n_descriptors) * 128);
-    check(mi_dmrecon_sift_get(ctx, kp.data(), xyso.data(), data.data()), "mi_dmrecon_sift_get");
+    mi_shim::check_args(mi_dmrecon_sift_get(ctx, kp.data(), xyso.data(), data.data()), "mi_dmrecon_sift_get");
 
     this->keypoints.resize(n_keypoints);
     for (int32_t i = 0; i < n_keypoints; ++i)

@@ -14,8 +14,9 @@
  * then the bytes.  process is one mi_dmrecon_surf_run + mi_dmrecon_surf_get on the GPU and, like the reference, releases
  * `sat`.  The protected stage members have no other caller and throw std::logic_error.
  *
- * One context for the process, made by the first call on the first entry of MI_DMRECON_DEVICES (default 0), as the other
- * shims read it; every calling thread works on its own fork (its own stream and buffers); all are released at exit.
+ * One context for the process, shared with every other drop-in of this directory that the binary links (shim_common.h): made
+ * by the first call of any of them on the first entry of MI_DMRECON_DEVICES (default 0); every calling thread works on its
+ * own fork (its own stream and buffers); all are released at exit.
  */
 #include <cstdint>
 #include <cstdlib>
@@ -31,71 +32,9 @@
 #include "mve/image.h"
 #include "sfm/surf.h"
 
-#include "mi_dmrecon.h"
+#include "shim_common.h"
 
 SFM_NAMESPACE_BEGIN
-
-namespace {
-
-int first_device(void)
-{
-    int const n = mi_dmrecon_device_count();
-    if (n <= 0)
-        throw std::runtime_error("sfm::Surf (MI355X build): no HIP device available; there is no CPU path");
-    char const* env = std::getenv("MI_DMRECON_DEVICES");
-    if (env && *env)
-    {
-        std::stringstream ss(env);
-        std::string tok;
-        while (std::getline(ss, tok, ','))
-        {
-            int const d = std::atoi(tok.c_str());
-            if (d >= 0 && d < n)
-                return d;
-        }
-    }
-    return 0;
-}
-
-void check(int rc, char const* what)
-{
-    if (rc == MI_DMRECON_EINVAL)
-        throw std::invalid_argument(mi_dmrecon_last_error());
-    if (rc != 0)
-        throw std::runtime_error(std::string(what) + ": " + mi_dmrecon_last_error());
-}
-
-/* the process-wide context and its forks */
-struct Contexts
-{
-    std::mutex mutex;
-    mi_dmrecon_ctx* parent = nullptr;
-    std::vector<mi_dmrecon_ctx*> forks;
-    ~Contexts (void)
-    {
-        for (std::size_t i = 0; i < this->forks.size(); ++i)
-            mi_dmrecon_ctx_destroy(this->forks[i]);
-        if (this->parent != nullptr)
-            mi_dmrecon_ctx_destroy(this->parent);
-    }
-};
-
-Contexts contexts;
-
-mi_dmrecon_ctx* context_of_this_thread(void)
-{
-    static thread_local mi_dmrecon_ctx* mine = nullptr;
-    if (mine != nullptr)
-        return mine;
-    std::lock_guard<std::mutex> lock(contexts.mutex);
-    if (contexts.parent == nullptr)
-        check(mi_dmrecon_ctx_create(first_device(), &contexts.parent), "mi_dmrecon_ctx_create");
-    check(mi_dmrecon_ctx_fork(contexts.parent, &mine), "mi_dmrecon_ctx_fork");
-    contexts.forks.push_back(mine);
-    return mine;
-}
-
-}  /* namespace */
 
 Surf::Surf (Options const& options)
     : options(options)
@@ -135,14 +74,14 @@ Surf::process (void)
     opt.contrast_threshold = this->options.contrast_threshold;
     opt.use_upright_descriptor = this->options.use_upright_descriptor ? 1 : 0;
 
-    mi_dmrecon_ctx* ctx = context_of_this_thread();
+    mi_dmrecon_ctx* ctx = mi_shim::context_of_this_thread("sfm::Surf");
     int32_t n_keypoints = 0, n_descriptors = 0;
-    check(mi_dmrecon_surf_run(ctx, &opt, reinterpret_cast<uint8_t const*>(&this->sat->at(3)), static_cast<int32_t>(this->sat->at(0)),
+    mi_shim::check_args(mi_dmrecon_surf_run(ctx, &opt, reinterpret_cast<uint8_t const*>(&this->sat->at(3)), static_cast<int32_t>(this->sat->at(0)),
         static_cast<int32_t>(this->sat->at(1)), static_cast<int32_t>(this->sat->at(2)), &n_keypoints, &n_descriptors),
         "mi_dmrecon_surf_run");
     this->keypoints.resize(n_keypoints);
     std::vector<float> xyso(static_cast<std::size_t>(n_descriptors) * 4), data(static_cast<std::size_t>(n_descriptors) * 64);
-    check(mi_dmrecon_surf_get(ctx, reinterpret_cast<mi_dmrecon_surf_keypoint*>(this->keypoints.data()), xyso.data(), data.data()),
+    mi_shim::check_args(mi_dmrecon_surf_get(ctx, reinterpret_cast<mi_dmrecon_surf_keypoint*>(this->keypoints.data()), xyso.data(), data.data()),
         "mi_dmrecon_surf_get");
 
     if (this->options.debug_output)
