@@ -1,10 +1,10 @@
 /*
  * mi_dmrecon_debug.h -- test and development hooks of libmi_dmrecon.so.
  *
- * NOT part of the drop-in boundary (include/mi_dmrecon.h is; nothing here replaces anything of the reference): these nine
+ * NOT part of the drop-in boundary (include/mi_dmrecon.h is; nothing here replaces anything of the reference): these eleven
  * entry points exist for tests/ and tools/ -- fault injection, the host-only halves of the planning (so that they can be
- * checked against the oracle without a GPU), pool introspection, the probe buffer of -DMI_PROBE builds, and the stored
- * bytes and the batching of the descriptor matching.  They are
+ * checked against the oracle without a GPU), pool introspection, the probe buffer of -DMI_PROBE builds, the stored
+ * bytes and the batching of the descriptor matching, and the stages and the list capacities of SIFT.  They are
  * declared here so that the library exports nothing that no header declares (the link uses a version script: only
  * mi_dmrecon_* symbols leave the library, tests/test_abi_and_host.py checks that every one of them is declared in one of
  * the two headers).  A production caller never needs them; they may change without notice.
@@ -65,6 +65,29 @@ int mi_dmrecon_debug_match_limits(long long entries, long long blocks);
  * or MI_DMRECON_EINVAL for a job that needs more workgroups than the limit.  The function the call itself runs on; needs no GPU. */
 int mi_dmrecon_debug_match_plan(int32_t n_jobs, const int32_t* n_a, const int32_t* n_b, long long entries, long long blocks,
                                 int32_t* batch_out, int32_t* block0_out, int32_t* col_chunks_out, int64_t* entry0_out);
+
+/* mi_dmrecon_sift_run's plan and image chain up to and including the octave in plan slot `slot` (0: the first octave, which is
+ * octave min_octave), through the code that call runs, and what the device holds of that octave afterwards.  Every output
+ * pointer may be NULL.  w_out, h_out: the octave's size; gray_out: the w x h gray image; src_out: the octave's source image,
+ * the input of blur 0; img_out, dog_out: the S + 3 Gaussian and the S + 2 DoG images, one behind the other; ks_out, wsum_out
+ * (S + 3 each) and taps_out ((S + 3) x 68, i = -ks ... ks first, zeros behind): the taps of each blur as the host made them
+ * (ks = 0: a copy); n_cand_out: the octave's extrema, not capped; cand_out (x | y << 16 and the sample, two words per entry)
+ * and loc_out (x, y, sample, kept per entry): the first min(*n_cand_out, the list's capacity, cand_room) entries.  raw_cand_out, raw_kp_out
+ * (mi_dmrecon_sift_keypoint) and raw_xyso_out (four floats): the first raw_room entries of the three lists' memory as it
+ * lies there, behind the capacities too (what a dropped write must have left alone); MI_DMRECON_EINVAL where the context
+ * never allocated that many.  Runs the kernels once, whatever overflows.  Leaves the context without a result for
+ * mi_dmrecon_sift_get. */
+int mi_dmrecon_debug_sift_octave(mi_dmrecon_ctx* ctx, const mi_dmrecon_sift_options* opt, const void* pixels, int32_t is_float, int32_t w,
+                                 int32_t h, int32_t channels, int32_t slot, int32_t* w_out, int32_t* h_out, float* gray_out, float* src_out,
+                                 float* img_out, float* dog_out, int32_t* ks_out, float* wsum_out, float* taps_out, int32_t cand_room,
+                                 int32_t* n_cand_out, int32_t* cand_out, float* loc_out, int32_t raw_room, int32_t* raw_cand_out,
+                                 void* raw_kp_out, float* raw_xyso_out);
+
+/* The capacities of the context's three SIFT lists (extrema of an octave, keypoints, descriptors) for the runs that follow: what
+ * the next mi_dmrecon_sift_run starts with; a run that overflows one grows it and runs again, and the context keeps what it
+ * grew.  0 restores a default; MI_DMRECON_EINVAL for a negative value.  Returns how often the context's last
+ * mi_dmrecon_sift_run went through its kernels (1: no list overflowed; 0: there was no run). */
+int mi_dmrecon_debug_sift_caps(mi_dmrecon_ctx* ctx, int32_t cand, int32_t kp, int32_t desc);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,7 @@ DEBUG_EXPORTS = [
     "mi_dmrecon_debug_inject_footprint", "mi_dmrecon_debug_front_teams", "mi_dmrecon_debug_plan_views_host",
     "mi_dmrecon_debug_scratch_sets", "mi_dmrecon_debug_region_mark", "mi_dmrecon_debug_buffer",
     "mi_dmrecon_debug_match_get", "mi_dmrecon_debug_match_limits", "mi_dmrecon_debug_match_plan",
+    "mi_dmrecon_debug_sift_octave", "mi_dmrecon_debug_sift_caps",
 ]
 
 MATCH_SIFT, MATCH_SURF = 0, 1      # MI_DMRECON_MATCH_SIFT / _SURF: 128 unsigned dims / 64 signed dims
@@ -296,6 +297,11 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_debug_match_get.argtypes = [vp, i32, i32, vp, vp]
         L.mi_dmrecon_debug_match_limits.argtypes = [ll, ll]
         L.mi_dmrecon_debug_match_plan.argtypes = [i32, vp, vp, ll, ll, vp, vp, vp, vp]
+    if hasattr(L, "mi_dmrecon_debug_sift_octave"):                                                           # test hooks
+        pi32 = ctypes.POINTER(i32)
+        L.mi_dmrecon_debug_sift_octave.argtypes = [vp, ctypes.POINTER(CSiftOptions), vp, i32, i32, i32, i32, i32, pi32, pi32, vp, vp, vp, vp,
+                                                   vp, vp, vp, i32, pi32, vp, vp, i32, vp, vp, vp]
+        L.mi_dmrecon_debug_sift_caps.argtypes = [vp, i32, i32, i32]
     _lib = L
     return L
 
@@ -892,6 +898,48 @@ class Context:
         if rc < 0:
             _raise(rc)
         return kp, xyso, desc
+
+    def debug_sift_octave(self, image, slot: int, raw_room: int = 0, **options):
+        """Test hook (mi_dmrecon_debug_sift_octave): Context.sift's plan and image chain up to and including the octave in
+        plan slot ``slot``, and what the device holds of it.  Returns dict(w, h, gray (H, W), src (h, w), img (S + 3, h, w),
+        dog (S + 2, h, w), ks (S + 3), wsum (S + 3), taps (S + 3, 68), n_cand (not capped), cand (n, 3) int32 x y sample,
+        loc (n, 4) float32 x y sample kept) and, with ``raw_room``, raw_cand (raw_room, 2) int32, raw_kp (SIFT_KEYPOINT) and raw_xyso
+        (raw_room, 4): the first raw_room entries of the three lists' memory as it lies there, behind the capacities too."""
+        _need(self._L, "mi_dmrecon_debug_sift_octave")
+        img, w, h, channels, o = _feature_input("sift", image, (np.uint8, np.float32), SIFT_DEFAULTS, options)
+        opt = CSiftOptions(*[o[f] for f, _ in CSiftOptions._fields_])
+        S = int(o["num_samples_per_octave"])
+        ow, oh, n_cand = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+
+        def call(*outputs):
+            rc = self._L.mi_dmrecon_debug_sift_octave(self._h, ctypes.byref(opt), _ptr(img), int(img.dtype == np.float32), w, h, channels,
+                                                      int(slot), ctypes.byref(ow), ctypes.byref(oh), *outputs)
+            if rc < 0:
+                _raise(rc)
+
+        call(None, None, None, None, None, None, None, 0, ctypes.byref(n_cand), None, None, 0, None, None, None)     # the sizes first
+        r = dict(w=ow.value, h=oh.value, gray=np.zeros((h, w), np.float32), src=np.zeros((oh.value, ow.value), np.float32),
+                 img=np.zeros((S + 3, oh.value, ow.value), np.float32), dog=np.zeros((S + 2, oh.value, ow.value), np.float32),
+                 ks=np.zeros(S + 3, np.int32), wsum=np.zeros(S + 3, np.float32), taps=np.zeros((S + 3, 68), np.float32))
+        cand, loc = np.zeros((n_cand.value, 2), np.int32), np.zeros((n_cand.value, 4), np.float32)
+        raw = (np.zeros((raw_room, 2), np.int32), np.zeros(raw_room, SIFT_KEYPOINT), np.zeros((raw_room, 4), np.float32))
+        call(_ptr(r["gray"]), _ptr(r["src"]), _ptr(r["img"]), _ptr(r["dog"]), _ptr(r["ks"]), _ptr(r["wsum"]), _ptr(r["taps"]), n_cand.value,
+             ctypes.byref(n_cand), _ptr(cand), _ptr(loc), int(raw_room), *[_ptr(a) if raw_room else None for a in raw])
+        if raw_room:
+            r["raw_cand"], r["raw_kp"], r["raw_xyso"] = raw
+        r["n_cand"] = n_cand.value
+        r["cand"] = np.stack([cand[:, 0] & 0xFFFF, cand[:, 0] >> 16, cand[:, 1]], axis=1)
+        r["loc"] = loc
+        return r
+
+    def debug_sift_caps(self, cand: int = 0, kp: int = 0, desc: int = 0) -> int:
+        """Test hook (mi_dmrecon_debug_sift_caps): the capacities of this context's three SIFT lists for the runs that follow
+        (0: the default).  Returns how often the context's last Context.sift went through its kernels (1: nothing overflowed)."""
+        _need(self._L, "mi_dmrecon_debug_sift_caps")
+        rc = self._L.mi_dmrecon_debug_sift_caps(self._h, int(cand), int(kp), int(desc))
+        if rc < 0:
+            _raise(rc)
+        return rc
 
     def surf(self, image, **options):
         """sfm::Surf::set_image + process (libs/sfm/surf.cc) for one image on the GPU (mi_dmrecon_surf_run, mi_dmrecon_surf_get).
