@@ -427,6 +427,56 @@ int  mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_
                             const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
                             int32_t* n_consistent);
 
+/* ---- sfm::CascadeHashing (libs/sfm/cascade_hashing.h, cascade_hashing.cc) on the same handle ----
+ *
+ * Per descriptor D = 128 / 64 hash bits (the signs of z . P_k, z = d / scale - mean in float, scale 255 / 127) and one bucket
+ * id per group; per set and group the features of each bucket in ascending id (build_buckets, cascade_hashing.cc:200-223);
+ * per query the candidates of its buckets ranked by the Hamming distance of the codes, and NearestNeighbor<T>::find over the
+ * best `min` ... `max` of them (oneway_match, collect_features_from_buckets, collect_top_ranked_candidates,
+ * cascade_hashing.h:328-471).
+ *
+ * What is exact and what is not.  Given the hash bits, everything after them is integer arithmetic and the two float tests
+ * of Matching::oneway_match: mi_dmrecon_match_pairs_hashed reproduces the reference's rules on the library's own bits
+ * exactly.  The bits are signs of float sums of 64 or 128 products; the reference is built with -funsafe-math-optimizations,
+ * so its order of summation is not defined.  NO bit-parity of the hash bits with a build of the reference is claimed: a sum
+ * within rounding of zero may fall either way (as for the RANSAC models and SIFT below).
+ *
+ * One deviation: a query without any candidate gives -1.  The reference would, with both tests passing, index an empty
+ * vector (cascade_hashing.h:413). */
+typedef struct mi_dmrecon_match_hash_options {
+    int32_t struct_size;         /* sizeof(mi_dmrecon_match_hash_options), set by the caller */
+    int32_t num_bucket_groups;   /* 1 ... 8, the reference's default: 6 */
+    int32_t num_bucket_bits;     /* 1 ... 8, default 8 (the reference reads the id back through a uint8_t, cascade_hashing.h:430) */
+    int32_t min_num_candidates;  /* default 6 */
+    int32_t max_num_candidates;  /* default 10; 1 <= min <= max <= 16 */
+} mi_dmrecon_match_hash_options;
+
+/* compute_cascade_hashes and build_buckets (cascade_hashing.h:258-311, cascade_hashing.cc:200-223) for every set's list of
+ * `kind` as it stands; the handle keeps the options.  mean [D], primary [D x D] and secondary [groups x bits x D], row per
+ * projection, are the caller's: the reference's mean is one float accumulation over all views (cascade_hashing.cc:145-177) and
+ * its matrices come from std::mt19937(0) with std::normal_distribution (cascade_hashing.h:225-254), so the library stays a
+ * function of its arguments.  A later mi_dmrecon_match_set on a set makes that set unhashed.
+ * MI_DMRECON_EINVAL, naming what is wrong, before anything is allocated or launched: a null handle or pointer; an unknown
+ * kind; struct_size not set; an option outside the ranges above; a mean or matrix entry that is not finite; a set of more
+ * than 2^24 / groups descriptors.  Not to be called while a pairs call runs on the same handle. */
+int  mi_dmrecon_match_hash(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_hash_options* opt, const float* mean,
+                           const float* primary, const float* secondary);
+
+/* The hashes of set `set`: returns its number n of descriptors of `kind` and fills codes [n x D / 64], the reference's
+ * comp_hash_data (the first projection of each 64 in the most significant bit), and bucket_ids [n x groups].  Either may be
+ * NULL.  MI_DMRECON_EINVAL for a set that is out of range, not hashed, or changed since it was hashed. */
+int  mi_dmrecon_match_hash_get(mi_dmrecon_match* m, int32_t set, int32_t kind, uint64_t* codes, uint16_t* bucket_ids);
+
+/* CascadeHashing::twoway_match (cascade_hashing.h:313-326) for n_jobs jobs in one launch, with the options of the last
+ * mi_dmrecon_match_hash of `kind`.  Outputs and conventions are those of mi_dmrecon_match_pairs: RAW one-way results, a job
+ * with an empty side all -1; a query without any candidate -1.  n_a and n_b must EQUAL the sizes of the two lists (the
+ * buckets are built for whole sets; CascadeHashing does not override pairwise_match_lowres).
+ * MI_DMRECON_EINVAL as for mi_dmrecon_match_pairs, and for: n_a or n_b different from the list's size; a set that is not
+ * hashed or was changed since.  May be called from several host threads on one handle at the same time. */
+int  mi_dmrecon_match_pairs_hashed(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs,
+                                   const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
+                                   int32_t* n_consistent);
+
 /* Frees the sets, streams and result buffers.  Destroy it before its context. */
 void mi_dmrecon_match_destroy(mi_dmrecon_match* m);
 

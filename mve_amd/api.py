@@ -47,6 +47,7 @@ EXPORTS = [
     "mi_dmrecon_patch_optimize", "mi_dmrecon_patch_eval", "mi_dmrecon_pointset",
     "mi_dmrecon_fssr_options_default", "mi_dmrecon_fssr_create", "mi_dmrecon_fssr_sample", "mi_dmrecon_fssr_destroy",
     "mi_dmrecon_match_create", "mi_dmrecon_match_set", "mi_dmrecon_match_pairs", "mi_dmrecon_match_destroy",
+    "mi_dmrecon_match_hash", "mi_dmrecon_match_hash_get", "mi_dmrecon_match_pairs_hashed",
     "mi_dmrecon_ransac_fundamental", "mi_dmrecon_ransac_sweep_capped",
     "mi_dmrecon_ransac_homography", "mi_dmrecon_ransac_pose_three_point",
     "mi_dmrecon_sift_run", "mi_dmrecon_sift_get",
@@ -108,6 +109,15 @@ class CMatchOptions(ctypes.Structure):
 
 class CMatchJob(ctypes.Structure):
     _fields_ = [("set_a", ctypes.c_int32), ("n_a", ctypes.c_int32), ("set_b", ctypes.c_int32), ("n_b", ctypes.c_int32)]
+
+
+class CMatchHashOptions(ctypes.Structure):
+    """mi_dmrecon_match_hash_options = sfm::CascadeHashing::Options (libs/sfm/cascade_hashing.h:32-45)."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("num_bucket_groups", ctypes.c_int32), ("num_bucket_bits", ctypes.c_int32),
+                ("min_num_candidates", ctypes.c_int32), ("max_num_candidates", ctypes.c_int32)]
+
+
+CASHASH_DEFAULTS = dict(num_bucket_groups=6, num_bucket_bits=8, min_num_candidates=6, max_num_candidates=10)
 
 
 class CRansacJob(ctypes.Structure):
@@ -275,6 +285,10 @@ def load_library() -> ctypes.CDLL:
         L.mi_dmrecon_match_pairs.argtypes = [vp, i32, ctypes.POINTER(CMatchOptions), i32, vp, vp, vp, vp]
         L.mi_dmrecon_match_destroy.argtypes = [vp]
         L.mi_dmrecon_match_destroy.restype = None
+    if hasattr(L, "mi_dmrecon_match_hash"):
+        L.mi_dmrecon_match_hash.argtypes = [vp, i32, ctypes.POINTER(CMatchHashOptions), vp, vp, vp]
+        L.mi_dmrecon_match_hash_get.argtypes = [vp, i32, i32, vp, vp]
+        L.mi_dmrecon_match_pairs_hashed.argtypes = [vp, i32, ctypes.POINTER(CMatchOptions), i32, vp, vp, vp, vp]
     if hasattr(L, "mi_dmrecon_ransac_fundamental"):
         L.mi_dmrecon_ransac_fundamental.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.mi_dmrecon_ransac_sweep_capped.argtypes = [vp]
@@ -999,6 +1013,7 @@ class Matcher:
         self._L = ctx._L
         self._ctx = ctx                 # the handle lives on the context's device
         self._h = None
+        self._hash_groups = {}          # num_bucket_groups of the last hash, by kind
         _need(self._L, "mi_dmrecon_match_create", "mi_dmrecon_match_* entry points")
         h = ctypes.c_void_p()
         rc = self._L.mi_dmrecon_match_create(ctx._h, int(n_sets), ctypes.byref(h))
@@ -1032,6 +1047,59 @@ class Matcher:
     def pairs(self, kind: int, jobs, lowe_ratio: float, distance: float):
         """One two-way match per job (set_a, n_a, set_b, n_b), all in one call: a list of (matches_ab [n_a], matches_ba [n_b],
         n_consistent) with the RAW one-way results (-1: no match) and Matching::count_consistent_matches of the two."""
+        return self._pairs(self._L.mi_dmrecon_match_pairs, kind, jobs, lowe_ratio, distance)
+
+    def pairs_hashed(self, kind: int, jobs, lowe_ratio: float, distance: float):
+        """``pairs`` through the cascade hashes of the last ``hash`` (sfm::CascadeHashing::twoway_match,
+        libs/sfm/cascade_hashing.h:313-471); n_a and n_b of a job must be the sizes of the whole lists."""
+        _need(self._L, "mi_dmrecon_match_pairs_hashed", "mi_dmrecon_match_hash* entry points")
+        return self._pairs(self._L.mi_dmrecon_match_pairs_hashed, kind, jobs, lowe_ratio, distance)
+
+    def hash(self, kind: int, mean, primary, secondary, **options) -> None:
+        """Hashes every set's list of ``kind`` as it stands and builds its bucket lists (mi_dmrecon_match_hash): mean (D,),
+        primary (D, D) and secondary (groups, bits, D) float32, one row per projection; options: CASHASH_DEFAULTS."""
+        if self._h is None:
+            raise RuntimeError("the matcher is closed")
+        _need(self._L, "mi_dmrecon_match_hash", "mi_dmrecon_match_hash* entry points")
+        unknown = set(options) - set(CASHASH_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown cascade hashing options: %s" % ", ".join(sorted(unknown)))
+        o = dict(CASHASH_DEFAULTS, **options)
+        dims = {MATCH_SIFT: 128, MATCH_SURF: 64}.get(kind)
+        if dims is None:
+            raise ValueError("unknown descriptor kind %r" % (kind,))
+        mean = np.ascontiguousarray(mean, np.float32)
+        primary = np.ascontiguousarray(primary, np.float32)
+        secondary = np.ascontiguousarray(secondary, np.float32)
+        if mean.shape != (dims,) or primary.shape != (dims, dims):
+            raise ValueError("mean (%d,) and primary (%d, %d) expected" % (dims, dims, dims))
+        if secondary.shape != (o["num_bucket_groups"], o["num_bucket_bits"], dims):
+            raise ValueError("secondary: (num_bucket_groups, num_bucket_bits, %d) expected" % dims)
+        opt = CMatchHashOptions(ctypes.sizeof(CMatchHashOptions), *[int(o[k]) for k in CASHASH_DEFAULTS])
+        rc = self._L.mi_dmrecon_match_hash(self._h, int(kind), ctypes.byref(opt), _ptr(mean), _ptr(primary), _ptr(secondary))
+        if rc < 0:
+            _raise(rc)
+        self._hash_groups[kind] = o["num_bucket_groups"]
+
+    def hashes(self, i: int, kind: int):
+        """Set ``i``'s hashes of ``kind`` (mi_dmrecon_match_hash_get): (codes uint64 (n, D / 64) in the reference's word
+        layout, bucket_ids uint16 (n, groups))."""
+        if self._h is None:
+            raise RuntimeError("the matcher is closed")
+        _need(self._L, "mi_dmrecon_match_hash_get", "mi_dmrecon_match_hash* entry points")
+        words = {MATCH_SIFT: 2, MATCH_SURF: 1}[kind]
+        n = self._L.mi_dmrecon_match_hash_get(self._h, int(i), int(kind), None, None)
+        if n < 0:
+            _raise(n)
+        codes = np.zeros((n, words), np.uint64)
+        ids = np.zeros((n, self._hash_groups.get(kind, 0)), np.uint16)
+        if n:
+            rc = self._L.mi_dmrecon_match_hash_get(self._h, int(i), int(kind), _ptr(codes), _ptr(ids))
+            if rc < 0:
+                _raise(rc)
+        return codes, ids
+
+    def _pairs(self, entry, kind: int, jobs, lowe_ratio: float, distance: float):
         if self._h is None:
             raise RuntimeError("the matcher is closed")
         jobs = [tuple(int(v) for v in j) for j in jobs]
@@ -1043,8 +1111,8 @@ class Matcher:
         pba = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in ba])
         cnt = np.zeros(max(n, 1), np.int32)
         opt = CMatchOptions(ctypes.sizeof(CMatchOptions), lowe_ratio, distance)
-        rc = self._L.mi_dmrecon_match_pairs(self._h, int(kind), ctypes.byref(opt), n, ctypes.cast(cj, ctypes.c_void_p),
-                                            ctypes.cast(pab, ctypes.c_void_p), ctypes.cast(pba, ctypes.c_void_p), _ptr(cnt))
+        rc = entry(self._h, int(kind), ctypes.byref(opt), n, ctypes.cast(cj, ctypes.c_void_p),
+                   ctypes.cast(pab, ctypes.c_void_p), ctypes.cast(pba, ctypes.c_void_p), _ptr(cnt))
         if rc < 0:
             _raise(rc)
         return [(ab[k], ba[k], int(cnt[k])) for k in range(n)]

@@ -30,4 +30,53 @@ void mi_match_discretise(hipStream_t s, int kind, int32_t n, const float* src, i
  * matches[e] = the one-way match of entry e (matching.h:114-146). */
 void mi_match_launch(hipStream_t s, int kind, const MatchJobDev* jobs, int32_t n_jobs, int32_t n_blocks, int64_t n_entries,
                      unsigned long long* best, int32_t* matches, float square_lowe_thres, float square_dist_thres);
+
+/* ---- cascade hashing (libs/sfm/cascade_hashing.h, cascade_hashing.cc) ---------------------------------------------------- */
+
+#define CASHASH_MAX_GROUPS 8      /* bucket ids of a record */
+#define CASHASH_MAX_CANDIDATES 16 /* one candidate per lane of a query's 16 */
+#define CASHASH_BUCKETS 256       /* per group, whatever num_bucket_bits is: ids above 2^bits - 1 do not occur */
+#define CASHASH_TILE 64           /* descriptors a workgroup of k_cashash_codes stages in LDS */
+
+/* What the match kernel reads of a candidate, in one 32-byte load: the hash code in the reference's word layout (SURF: code[1]
+ * is 0) and the bucket id of every group (groups past num_bucket_groups: 0). */
+struct CashashRecord {
+    unsigned long long code[2];
+    uint8_t bucket[CASHASH_MAX_GROUPS];
+    uint8_t pad[8];
+};
+
+/* The hashed state of one descriptor list: n records; per group CASHASH_BUCKETS + 1 offsets and the n feature ids, those of a
+ * bucket contiguous and ascending (build_buckets, cascade_hashing.cc:200-223). */
+struct CashashSetDev {
+    const CashashRecord* rec;
+    const int32_t* bucket_off;    /* groups x (CASHASH_BUCKETS + 1) */
+    const int32_t* bucket_ids;    /* groups x n */
+    const int8_t* desc;
+    const int32_t* off;           /* MatchJobDev::off */
+    int32_t n;
+};
+
+/* One two-way job: entries entry0 ... + a.n - 1 are the queries of a against b, the next b.n those of b against a. */
+struct CashashJobDev {
+    CashashSetDev a, b;           /* both n > 0 */
+    int64_t entry0;
+};
+
+struct CashashParams {
+    int32_t groups, bits, min_candidates, max_candidates;
+};
+
+/* compute_cascade_hashes (cascade_hashing.h:258-311) of n stored descriptors.  proj: ceil(D / 64) + 1 blocks of D x 64 floats,
+ * block k < D / 64 holding the primary projections 64 k ... 64 k + 63 and the last the groups * bits secondary ones, padded
+ * with zeros; within a block component-major (the 64 projections of a component are contiguous). */
+void mi_cashash_codes(hipStream_t s, int kind, int32_t n, const int8_t* desc, const float* mean, const float* proj,
+                      CashashParams p, CashashRecord* rec);
+
+/* build_buckets from the records: no global atomics, the same bytes on every run. */
+void mi_cashash_buckets(hipStream_t s, int32_t n, const CashashRecord* rec, CashashParams p, int32_t* bucket_off, int32_t* bucket_ids);
+
+/* CascadeHashing::oneway_match (cascade_hashing.h:328-471) of every entry of every job, both directions, in one launch. */
+void mi_cashash_match(hipStream_t s, int kind, const CashashJobDev* jobs, int32_t n_jobs, int64_t n_entries, CashashParams p,
+                      int32_t* matches, float square_lowe_thres, float square_dist_thres);
 #endif

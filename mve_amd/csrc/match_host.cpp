@@ -33,13 +33,18 @@ struct MatchSet {
     int32_t n = 0;
     int8_t* d_desc = nullptr;                /* n rows of 128 / 64 bytes */
     int32_t* d_off = nullptr;                /* MatchJobDev::off */
+    /* cascade hashing: set by mi_dmrecon_match_hash, gone with the list (free_set) */
+    bool hashed = false;
+    CashashRecord* d_rec = nullptr;          /* n */
+    int32_t* d_bucket_off = nullptr;         /* groups x (CASHASH_BUCKETS + 1) */
+    int32_t* d_bucket_ids = nullptr;         /* groups x n */
 };
 
 /* A stream and the buffers of one call; they grow only. */
 struct MatchSlot {
     hipStream_t stream = nullptr;
     bool busy = false;
-    Buf d_jobs;                              /* MatchJobDev per job */
+    Buf d_jobs;                              /* MatchJobDev or CashashJobDev per job */
     Buf d_best;                              /* two unsigned long long per row and column ... */
     Buf d_matches;                           /* ... and one int32_t */
     PinnedBuf h_matches;
@@ -51,6 +56,7 @@ struct mi_dmrecon_match {
     int device = -1;
     int32_t n_sets = 0;
     std::vector<MatchSet> sets[2];           /* by kind */
+    CashashParams hash_params[2] = {};       /* of the last mi_dmrecon_match_hash, by kind */
     std::mutex mu;
     std::condition_variable cv;
     MatchSlot slots[MATCH_SLOTS];
@@ -60,7 +66,16 @@ namespace {
 
 int dims_of(int kind) { return kind == MATCH_SIFT ? 128 : 64; }
 
+void free_hash(MatchSet& s) {
+    if (s.d_rec) (void)hipFree(s.d_rec);
+    if (s.d_bucket_off) (void)hipFree(s.d_bucket_off);
+    if (s.d_bucket_ids) (void)hipFree(s.d_bucket_ids);
+    s.d_rec = nullptr; s.d_bucket_off = nullptr; s.d_bucket_ids = nullptr;
+    s.hashed = false;
+}
+
 void free_set(MatchSet& s) {
+    free_hash(s);
     if (s.d_desc) (void)hipFree(s.d_desc);
     if (s.d_off) (void)hipFree(s.d_off);
     s = MatchSet();
@@ -184,11 +199,11 @@ int count_consistent(const int32_t* ab, int32_t n_a, const int32_t* ba) {   /* M
     return counter;
 }
 
-int grow(MatchSlot& s, size_t n_jobs, size_t n_entries) {
+int grow(MatchSlot& s, size_t job_bytes, size_t n_entries, bool keys) {
     if (!s.stream) MI_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    MI_HIP(s.d_jobs.need(std::max<size_t>(n_jobs, 256) * sizeof(MatchJobDev)));
-    /* (the three are asked for the same number of entries every time, so they grow together) */
-    MI_HIP(s.d_best.need(n_entries * 2 * sizeof(unsigned long long)));
+    MI_HIP(s.d_jobs.need(std::max<size_t>(job_bytes, 256 * sizeof(MatchJobDev))));
+    /* (asked for the same number of entries every time, so they grow together; the hashed path keeps no keys) */
+    if (keys) MI_HIP(s.d_best.need(n_entries * 2 * sizeof(unsigned long long)));
     MI_HIP(s.d_matches.need(n_entries * sizeof(int32_t)));
     MI_HIP(s.h_matches.need(n_entries * sizeof(int32_t)));
     return 0;
@@ -288,7 +303,7 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
             blocks = plan[j].block0 + job_blocks(q.n_a, q.n_b); entries = plan[j].entry0 + q.n_a + q.n_b;
         }
         if (dev.empty()) break;
-        if (int rc = grow(s, dev.size(), (size_t)entries)) return rc;
+        if (int rc = grow(s, dev.size() * sizeof(MatchJobDev), (size_t)entries, true)) return rc;
         MI_HIP(hipMemcpyAsync(s.d_jobs.p, dev.data(), dev.size() * sizeof(MatchJobDev), hipMemcpyHostToDevice, s.stream));
         MI_HIP(hipMemsetAsync(s.d_best.p, 0, (size_t)entries * 2 * sizeof(unsigned long long), s.stream));
         mi_match_launch(s.stream, kind, (const MatchJobDev*)s.d_jobs.p, (int32_t)dev.size(), (int32_t)blocks, entries,
@@ -303,6 +318,181 @@ int pairs_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options
             if (matches_ab && matches_ab[jj]) std::memcpy(matches_ab[jj], ab, (size_t)dev[k].n_a * sizeof(int32_t));
             if (matches_ba && matches_ba[jj]) std::memcpy(matches_ba[jj], ba, (size_t)dev[k].n_b * sizeof(int32_t));
             if (n_consistent) n_consistent[jj] = count_consistent(ab, dev[k].n_a, ba);
+        }
+    }
+    return 0;
+}
+
+/* ---- cascade hashing ---------------------------------------------------------------------------------------------------- */
+
+bool all_finite(const float* v, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (!(v[i] - v[i] == 0.0f)) return false;
+    return true;
+}
+
+int hash_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_hash_options* opt, const float* mean, const float* primary,
+              const float* secondary) {
+    if (!m) return failf(MI_DMRECON_EINVAL, "match: null handle");
+    if (kind != MATCH_SIFT && kind != MATCH_SURF) return failf(MI_DMRECON_EINVAL, "match: unknown descriptor kind %lld", kind);
+    if (!opt || opt->struct_size < (int32_t)sizeof(mi_dmrecon_match_hash_options))
+        return failf(MI_DMRECON_EINVAL, "match: hash options missing or their struct_size not set");
+    if (opt->num_bucket_groups < 1 || opt->num_bucket_groups > CASHASH_MAX_GROUPS)
+        return failf(MI_DMRECON_EINVAL, "match: num_bucket_groups %lld outside 1 ... 8", opt->num_bucket_groups);
+    if (opt->num_bucket_bits < 1 || opt->num_bucket_bits > 8)
+        return failf(MI_DMRECON_EINVAL, "match: num_bucket_bits %lld outside 1 ... 8", opt->num_bucket_bits);
+    if (opt->min_num_candidates < 1 || opt->min_num_candidates > opt->max_num_candidates || opt->max_num_candidates > CASHASH_MAX_CANDIDATES)
+        return failf(MI_DMRECON_EINVAL, "match: min_num_candidates %lld, max_num_candidates %lld: 1 <= min <= max <= 16 wanted",
+                     opt->min_num_candidates, opt->max_num_candidates);
+    if (!mean || !primary || !secondary) return failf(MI_DMRECON_EINVAL, "match: null mean or projection matrix");
+    const int D = dims_of(kind);
+    const CashashParams p = { opt->num_bucket_groups, opt->num_bucket_bits, opt->min_num_candidates, opt->max_num_candidates };
+    const int n_secondary = p.groups * p.bits;
+    if (!all_finite(mean, D)) return failf(MI_DMRECON_EINVAL, "match: the mean has an entry that is not finite");
+    if (!all_finite(primary, (size_t)D * D)) return failf(MI_DMRECON_EINVAL, "match: the primary matrix has an entry that is not finite");
+    if (!all_finite(secondary, (size_t)n_secondary * D))
+        return failf(MI_DMRECON_EINVAL, "match: the secondary matrices have an entry that is not finite");
+
+    std::lock_guard<std::mutex> lock(m->mu);
+    std::vector<MatchSet>& sets = m->sets[kind];
+    for (int32_t i = 0; i < m->n_sets; ++i)                    /* seq, a position in the walk of groups buckets, must fit 24 bits */
+        if (sets[i].n > (1 << 24) / p.groups)
+            return failf(MI_DMRECON_EINVAL, "match: set %lld holds %lld descriptors, more than 2^24 / %lld groups", i, sets[i].n, p.groups);
+
+    /* blocks of 64 projections, component-major (k_cashash_codes): the code words, then the secondary projections */
+    const int words = D / 64;
+    std::vector<float> proj((size_t)(words + 1) * D * 64, 0.0f);
+    for (int k = 0; k < D; ++k)
+        for (int i = 0; i < D; ++i) proj[((size_t)(k / 64) * D + i) * 64 + k % 64] = primary[(size_t)k * D + i];
+    for (int k = 0; k < n_secondary; ++k)
+        for (int i = 0; i < D; ++i) proj[((size_t)words * D + i) * 64 + k] = secondary[(size_t)k * D + i];
+
+    MI_HIP(hipSetDevice(m->device));
+    for (MatchSet& s : sets) free_hash(s);
+    Buf d_mean, d_proj;
+    hipError_t e = d_mean.need(D * sizeof(float));
+    if (e == hipSuccess) e = d_proj.need(proj.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_mean.p, mean, D * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_proj.p, proj.data(), proj.size() * sizeof(float), hipMemcpyHostToDevice);
+    for (int32_t i = 0; i < m->n_sets && e == hipSuccess; ++i) {
+        MatchSet& s = sets[i];
+        if (s.n == 0) continue;
+        e = hipMalloc((void**)&s.d_rec, (size_t)s.n * sizeof(CashashRecord));
+        if (e == hipSuccess) e = hipMalloc((void**)&s.d_bucket_off, (size_t)p.groups * (CASHASH_BUCKETS + 1) * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&s.d_bucket_ids, (size_t)p.groups * s.n * sizeof(int32_t));
+        if (e != hipSuccess) break;
+        mi_cashash_codes(nullptr, kind, s.n, s.d_desc, (const float*)d_mean.p, (const float*)d_proj.p, p, s.d_rec);
+        mi_cashash_buckets(nullptr, s.n, s.d_rec, p, s.d_bucket_off, s.d_bucket_ids);
+        e = hipGetLastError();
+    }
+    const hipError_t e_sync = hipStreamSynchronize(nullptr);   /* (before d_mean and d_proj go) */
+    if (e == hipSuccess) e = e_sync;
+    if (e != hipSuccess) {
+        for (MatchSet& s : sets) free_hash(s);
+        char b[200];
+        std::snprintf(b, sizeof(b), "match: hashing failed: %s", hipGetErrorString(e));
+        return mi_host_fail(MI_DMRECON_EDEVICE, b);
+    }
+    for (MatchSet& s : sets) s.hashed = true;
+    m->hash_params[kind] = p;
+    return 0;
+}
+
+int hash_get_impl(mi_dmrecon_match* m, int32_t set, int32_t kind, uint64_t* codes, uint16_t* bucket_ids) {
+    if (!m) return failf(MI_DMRECON_EINVAL, "match: null handle");
+    if (kind != MATCH_SIFT && kind != MATCH_SURF) return failf(MI_DMRECON_EINVAL, "match: unknown descriptor kind %lld", kind);
+    if (set < 0 || set >= m->n_sets) return failf(MI_DMRECON_EINVAL, "match: set %lld outside [0, %lld)", set, m->n_sets);
+    std::lock_guard<std::mutex> lock(m->mu);
+    const MatchSet& s = m->sets[kind][set];
+    if (!s.hashed) return failf(MI_DMRECON_EINVAL, "match: set %lld is not hashed, or was changed since it was hashed", set);
+    if (s.n == 0 || (!codes && !bucket_ids)) return s.n;
+    MI_HIP(hipSetDevice(m->device));
+    std::vector<CashashRecord> rec(s.n);
+    MI_HIP(hipMemcpy(rec.data(), s.d_rec, (size_t)s.n * sizeof(CashashRecord), hipMemcpyDeviceToHost));
+    const int words = dims_of(kind) / 64, groups = m->hash_params[kind].groups;
+    for (int32_t i = 0; i < s.n; ++i) {
+        for (int w = 0; codes && w < words; ++w) codes[(size_t)i * words + w] = rec[i].code[w];
+        for (int g = 0; bucket_ids && g < groups; ++g) bucket_ids[(size_t)i * groups + g] = rec[i].bucket[g];
+    }
+    return s.n;
+}
+
+CashashSetDev hashed_set(const MatchSet& s) {
+    CashashSetDev d;
+    d.rec = s.d_rec; d.bucket_off = s.d_bucket_off; d.bucket_ids = s.d_bucket_ids; d.desc = s.d_desc; d.off = s.d_off; d.n = s.n;
+    return d;
+}
+
+int pairs_hashed_impl(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs, const mi_dmrecon_match_job* jobs,
+                      int32_t* const* matches_ab, int32_t* const* matches_ba, int32_t* n_consistent) {
+    if (!m) return failf(MI_DMRECON_EINVAL, "match: null handle");
+    if (kind != MATCH_SIFT && kind != MATCH_SURF) return failf(MI_DMRECON_EINVAL, "match: unknown descriptor kind %lld", kind);
+    if (!opt || opt->struct_size < (int32_t)sizeof(mi_dmrecon_match_options))
+        return failf(MI_DMRECON_EINVAL, "match: options missing or their struct_size not set");
+    if (n_jobs < 0) return failf(MI_DMRECON_EINVAL, "match: negative number of jobs");
+    if (n_jobs == 0) return 0;
+    if (!jobs) return failf(MI_DMRECON_EINVAL, "match: null jobs");
+
+    std::vector<MatchSet> sets;
+    CashashParams p;
+    {
+        std::lock_guard<std::mutex> lock(m->mu);
+        sets = m->sets[kind];
+        p = m->hash_params[kind];
+    }
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        const mi_dmrecon_match_job& q = jobs[j];
+        if (q.set_a < 0 || q.set_a >= m->n_sets || q.set_b < 0 || q.set_b >= m->n_sets)
+            return failf(MI_DMRECON_EINVAL, "match: job %lld names a set outside [0, %lld)", j, m->n_sets);
+        if (!sets[q.set_a].hashed || !sets[q.set_b].hashed)
+            return failf(MI_DMRECON_EINVAL, "match: job %lld names a set that is not hashed, or was changed since it was hashed", j);
+        if (q.n_a != sets[q.set_a].n || q.n_b != sets[q.set_b].n)
+            return failf(MI_DMRECON_EINVAL, "match: job %lld: the hashed match takes whole lists (%lld and %lld descriptors)", j,
+                         sets[q.set_a].n, sets[q.set_b].n);
+    }
+    const float square_lowe_thres = opt->lowe_ratio_threshold * opt->lowe_ratio_threshold;      /* MATH_POW2 in float */
+    const float square_dist_thres = opt->distance_threshold * opt->distance_threshold;
+
+    SlotLease lease(m);
+    MatchSlot& s = *lease.slot;
+    MI_HIP(hipSetDevice(m->device));
+    const long long lim_entries = g_batch_entries.load();
+    std::vector<CashashJobDev> dev;
+    std::vector<int32_t> which;
+    for (int32_t j = 0; j < n_jobs;) {
+        /* a batch: jobs in order while their queries fit the limit (one job above it goes alone) */
+        dev.clear(); which.clear();
+        long long entries = 0;
+        for (; j < n_jobs; ++j) {
+            const mi_dmrecon_match_job& q = jobs[j];
+            if (q.n_a == 0 || q.n_b == 0) {                    /* an empty side: all -1 (cascade_hashing.h:341-342) */
+                if (matches_ab && matches_ab[j]) std::fill(matches_ab[j], matches_ab[j] + q.n_a, -1);
+                if (matches_ba && matches_ba[j]) std::fill(matches_ba[j], matches_ba[j] + q.n_b, -1);
+                if (n_consistent) n_consistent[j] = 0;
+                continue;
+            }
+            const long long ne = (long long)q.n_a + q.n_b;
+            if (!dev.empty() && entries + ne > lim_entries) break;
+            CashashJobDev d;
+            d.a = hashed_set(sets[q.set_a]); d.b = hashed_set(sets[q.set_b]); d.entry0 = entries;
+            dev.push_back(d); which.push_back(j);
+            entries += ne;
+        }
+        if (dev.empty()) break;
+        if (int rc = grow(s, dev.size() * sizeof(CashashJobDev), (size_t)entries, false)) return rc;
+        MI_HIP(hipMemcpyAsync(s.d_jobs.p, dev.data(), dev.size() * sizeof(CashashJobDev), hipMemcpyHostToDevice, s.stream));
+        mi_cashash_match(s.stream, kind, (const CashashJobDev*)s.d_jobs.p, (int32_t)dev.size(), entries, p, (int32_t*)s.d_matches.p,
+                         square_lowe_thres, square_dist_thres);
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipMemcpyAsync(s.h_matches.p, s.d_matches.p, (size_t)entries * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
+        MI_HIP(hipStreamSynchronize(s.stream));       /* (before `dev` changes: the copy above may still read it) */
+        for (size_t k = 0; k < dev.size(); ++k) {
+            const int32_t jj = which[k];
+            const int32_t* ab = (const int32_t*)s.h_matches.p + dev[k].entry0;
+            const int32_t* ba = ab + dev[k].a.n;
+            if (matches_ab && matches_ab[jj]) std::memcpy(matches_ab[jj], ab, (size_t)dev[k].a.n * sizeof(int32_t));
+            if (matches_ba && matches_ba[jj]) std::memcpy(matches_ba[jj], ba, (size_t)dev[k].b.n * sizeof(int32_t));
+            if (n_consistent) n_consistent[jj] = count_consistent(ab, dev[k].a.n, ba);
         }
     }
     return 0;
@@ -324,6 +514,21 @@ int mi_dmrecon_match_pairs(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_m
                            const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
                            int32_t* n_consistent) {
     return guarded([&] { return pairs_impl(m, kind, opt, n_jobs, jobs, matches_ab, matches_ba, n_consistent); });
+}
+
+int mi_dmrecon_match_hash(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_hash_options* opt, const float* mean,
+                          const float* primary, const float* secondary) {
+    return guarded([&] { return hash_impl(m, kind, opt, mean, primary, secondary); });
+}
+
+int mi_dmrecon_match_hash_get(mi_dmrecon_match* m, int32_t set, int32_t kind, uint64_t* codes, uint16_t* bucket_ids) {
+    return guarded([&] { return hash_get_impl(m, set, kind, codes, bucket_ids); });
+}
+
+int mi_dmrecon_match_pairs_hashed(mi_dmrecon_match* m, int32_t kind, const mi_dmrecon_match_options* opt, int32_t n_jobs,
+                                  const mi_dmrecon_match_job* jobs, int32_t* const* matches_ab, int32_t* const* matches_ba,
+                                  int32_t* n_consistent) {
+    return guarded([&] { return pairs_hashed_impl(m, kind, opt, n_jobs, jobs, matches_ab, matches_ba, n_consistent); });
 }
 
 void mi_dmrecon_match_destroy(mi_dmrecon_match* m) { release(m); }

@@ -31,30 +31,18 @@
 #include "sfm/exhaustive_matching.h"
 
 #include "shim_common.h"
-
-SFM_NAMESPACE_BEGIN
+#include "sfm_matcher_registry.h"
 
 namespace {
 
-using mi_shim::check;
-
-/* the context and the matcher of one ExhaustiveMatching object */
-struct Device
-{
-    mi_dmrecon_ctx* ctx = nullptr;
-    mi_dmrecon_match* match = nullptr;
-    ~Device (void)
-    {
-        mi_dmrecon_match_destroy(this->match);
-        if (this->ctx != nullptr)
-            mi_dmrecon_ctx_destroy(this->ctx);
-    }
-};
+typedef mi_shim::MatcherDevice Device;
 
 std::mutex registry_mutex;
 std::map<void const*, std::shared_ptr<Device> > registry;      /* destroyed at process exit, and its handles with it */
 
-std::shared_ptr<Device> device_of(void const* self)
+}  /* namespace */
+
+std::shared_ptr<mi_shim::MatcherDevice> mi_shim::matcher_of(void const* self)
 {
     std::lock_guard<std::mutex> lock(registry_mutex);
     std::map<void const*, std::shared_ptr<Device> >::const_iterator it = registry.find(self);
@@ -62,6 +50,14 @@ std::shared_ptr<Device> device_of(void const* self)
         throw std::runtime_error("sfm::ExhaustiveMatching (MI355X build): pairwise_match before init");
     return it->second;
 }
+
+SFM_NAMESPACE_BEGIN
+
+namespace {
+
+using mi_shim::check;
+
+std::shared_ptr<Device> device_of(void const* self) { return mi_shim::matcher_of(self); }
 
 /* Matching::twoway_match of the first n_1 / n_2 descriptors of two views; raw, as the reference's */
 void twoway(Device const& dev, int kind, Matching::Options const& options, int view_1, std::size_t n_1, int view_2,

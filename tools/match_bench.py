@@ -2,6 +2,11 @@
 
     python tools/match_bench.py --build-ref [--ref /path/to/mve]     # where the reference tree exists: build/ref_match_bench
     python tools/match_bench.py [--sets 20] [--n 10000] [--repeats 5] [--cpu-repeats 2] [--threads 16] [--out FILE.json]
+    python tools/match_bench.py --cascade [--sets 20] [--n 10000] [--repeats 5] [--out FILE.json]
+
+--cascade: the same sets through mi_dmrecon_match_hash (N(0, 1) matrices, the mean of all descriptors) and
+mi_dmrecon_match_pairs_hashed, the exhaustive call and the hashed call ALTERNATING in one session; reports the median of
+each, the time of hashing the sets, and the share of the exhaustive path's consistent matches that the hashed path also finds.
 
 Workload: `--sets` SIFT sets of `--n` unit-norm descriptors (a fifth of each planted as near-duplicates of a shared pool),
 all sets * (sets - 1) / 2 pairs in ONE pairs call.  GPU: one warm-up call, then the median wall time of `--repeats` calls,
@@ -76,6 +81,53 @@ def make_sets(n_sets: int, n: int, seed: int = 7):
     return sets
 
 
+def cascade(a) -> None:
+    from mve_amd import api
+    assert api.device_count() > 0, "match_bench needs a HIP device"
+    sets = make_sets(a.sets, a.n)
+    jobs = [(i, a.n, j, a.n) for i in range(a.sets) for j in range(i + 1, a.sets)]
+    rng = np.random.default_rng(0)
+    primary = rng.standard_normal((128, 128)).astype(np.float32)
+    secondary = rng.standard_normal((6, 8, 128)).astype(np.float32)
+    mean = (np.concatenate([R.discretise(s, R.SIFT) for s in sets]).astype(np.float32) / np.float32(255)).mean(axis=0)
+    ctx = api.Context(0)
+    m = ctx.match_open(a.sets)
+    for v, s in enumerate(sets):
+        m.set(v, api.MATCH_SIFT, s)
+    t_hash = []
+    for _ in range(a.repeats + 1):                                   # (the first: code objects)
+        t0 = time.perf_counter()
+        m.hash(api.MATCH_SIFT, mean, primary, secondary)
+        t_hash.append(time.perf_counter() - t0)
+    entries = {"exhaustive": m.pairs, "hashed": m.pairs_hashed}
+    res, times = {}, {k: [] for k in entries}
+    for rep_ in range(a.repeats + 1):                                # (the first of each: warm-up)
+        for name, call in entries.items():
+            t0 = time.perf_counter()
+            res[name] = call(api.MATCH_SIFT, jobs, 0.8, FLT_MAX)
+            if rep_:
+                times[name].append(time.perf_counter() - t0)
+    m.close()
+    ctx.close()
+    kept = found = 0
+    for (ab, ba, _), (hab, hba, _) in zip(res["exhaustive"], res["hashed"]):
+        ok = (ab >= 0) & (ba[np.maximum(ab, 0)] == np.arange(len(ab)))
+        kept += int(ok.sum())
+        found += int((ok & (hab == ab) & (hba[np.maximum(ab, 0)] == np.arange(len(ab)))).sum())
+    out = dict(workload="%d SIFT sets x %d descriptors, %d pairs in one call" % (a.sets, a.n, len(jobs)),
+               hash_all_sets_s=[round(t, 5) for t in t_hash[1:]], hash_median_s=round(float(np.median(t_hash[1:])), 5),
+               exhaustive_call_s=[round(t, 5) for t in times["exhaustive"]], hashed_call_s=[round(t, 5) for t in times["hashed"]],
+               exhaustive_median_s=round(float(np.median(times["exhaustive"])), 5), hashed_median_s=round(float(np.median(times["hashed"])), 5),
+               exhaustive_consistent=kept, hashed_consistent=int(sum(r[2] for r in res["hashed"])), hashed_finds_of_exhaustive=found,
+               share=round(found / max(kept, 1), 4))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--build-ref", action="store_true")
@@ -86,9 +138,13 @@ def main() -> None:
     ap.add_argument("--cpu-repeats", type=int, default=2)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cascade", action="store_true")
     a = ap.parse_args()
     if a.build_ref:
         build_ref(a.ref)
+        return
+    if a.cascade:
+        cascade(a)
         return
 
     from mve_amd import api
